@@ -6,7 +6,17 @@ samples per utterance), fp16 activations / fp32 accumulation, synthetic mel ~ N(
 already resident in HBM, deterministic seeded weights (no checkpoint offline).
 A "step" = one vocoder forward over the batch.
 
-The same line also carries `full_pipeline` (configs[2]: token ids U[1,77] [32,144],
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the line: the headline fields and the headline's `roofline`, whose hipEvents sit inside the
+last timed step (no run of its own).  Everything below -- `full_pipeline`, `c4`, `streaming`, `c1`
+and `cpu_baseline` -- is measured only with `--full` (each part still has its `--no-*` switch).
+
+`--dump-outputs DIR` writes what the last timed step computed, the waveform a caller of the timed
+path receives, to DIR/wav.npy (float32 [batch, samples]; DIR/wav.rank<r>.npy per rank at N > 1)
+right after the timed steps.  Inputs and weights are seeded, so the same arguments give the same
+inputs from run to run and two builds can be compared output for output.
+
+With `--full` the same line also carries `full_pipeline` (configs[2]: token ids U[1,77] [32,144],
 durations forced to 6 frames/token -> 864 frames; acoustic bf16 + vocoder bf16,
 tokens in HBM -> waveform in HBM), measured after the headline loop, and beside it the host
 end-to-end rate (`host_e2e_*`: token ids in host memory -> waveform in pinned host memory,
@@ -21,7 +31,7 @@ Every rank checks that the process group has exactly N ranks (a 1-GPU box asked 
 --gpus 2 fails loudly).  Utterances are independent, so C2 runs a batch-32 shard per
 rank with no data-path collective (weak scaling); the timed loop is bracketed by
 barriers and the max time over ranks is used.  value = samples of all ranks / max time.
-The same line carries `c4` (configs[3]: 256 mixed-length utterances owned by rank 0,
+With `--full` the line carries `c4` (configs[3]: 256 mixed-length utterances owned by rank 0,
 RCCL broadcast -> per-rank length-bucketed synthesis -> RCCL P2P gather to rank 0 inside
 the timed region; strong scaling over N; at N=1 no process group exists and no collective
 runs, which the line says), `streaming` (configs[4], C5: p50 first audio with predicted
@@ -32,7 +42,7 @@ durations as a request runs it, beside the given-durations and fast-encoder vari
 fused ResBlock-pair kernel of all four stages), timed live with hipEvents around every launch
 on the stream it runs on; `roofline.kernels` lists every family the same way
 (conv_gemm_kernel, conv_xres_kernel, mrf_pair_kernel, mrf_chain_kernel, upsample_stream_kernel,
-conv_split_kernel).  `cpu_baseline` (rank 0, N=1 only) is the torch-CPU fp32
+conv_split_kernel).  `cpu_baseline` (`--full`; rank 0, N=1 only) is the torch-CPU fp32
 restatement (oracle/torch_cpu.py) timed on the host cores on a bounded
 sample of C2 (4 utterances), C3 (2 utterances) and C1 (one 71-token sentence).
 `full_pipeline.acoustic_roofline` is the acoustic forward against the MFMA peak (80.19 GFLOP
@@ -74,6 +84,11 @@ def parse():
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--workload", default="vocoder", choices=["vocoder", "full", "c4", "selftest"],
                     help="selftest: CPU-only gloo check of the launcher / process group (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: full_pipeline (C3), c4, streaming (C5), "
+                         "c1 and cpu_baseline (each can still be skipped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's waveform to DIR/wav.npy (float32)")
     ap.add_argument("--c4-batch", type=int, default=256)
     ap.add_argument("--c4-bucket", type=int, default=64, help="utterances per length bucket (one synthesis call; 64 measured best of 32/64/128)")
     ap.add_argument("--no-c4", action="store_true", help="skip the C4 sharded side measurement")
@@ -86,7 +101,28 @@ def parse():
     ap.add_argument("--selftest-fail-rank", type=int, default=-1,
                     help="selftest only: this rank exits with status 7 after joining the process group "
                          "(tests/test_bench_cpu.py: the launcher must end the run, not hang)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("vocoder", "full"):
+        ap.error("--dump-outputs: the vocoder and full workloads write their waveform; "
+                 f"--workload {args.workload} has no dump")
+    return args
+
+
+def dump_outputs(ctx, args, **arrays):
+    """--dump-outputs DIR: each device tensor -> DIR/<name>.npy in float32 (one file per rank at
+    N > 1).  C2 / C3 at the default shape are 28 MB; a larger output is cut to a fixed seeded
+    sample of its rows so that a dump stays under 64 MB."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    budget = (64 << 20) // (max(len(arrays), 1) * ctx.world)  # bytes per file: 64 MB over all ranks
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            rows = max(1, budget // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))]
+        suffix = f".rank{ctx.rank}" if ctx.world > 1 else ""
+        np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
 
 
 def launch_ranks(args) -> int:
@@ -377,6 +413,7 @@ def bench_vocoder(ctx, args):
     lens = torch.full((B,), T, dtype=torch.int32, device=ctx.dev)
     wav = torch.empty((B, T * 256), dtype=torch.float32, device=ctx.dev)
     el, prof = ctx.timed(lambda: eng.vocoder(mel, lens, out=wav), args.steps, args.warmup, eng)
+    dump_outputs(ctx, args, wav=wav)
     samples = B * T * 256 * args.steps * ctx.world
     value = samples / el
     out = {"value": value, "ms_per_step": el * 1e3 / args.steps, "samples_per_utt": T * 256,
@@ -406,6 +443,8 @@ def bench_full(ctx, args, steps, warmup):
         eng.vocoder(mel, mel_lens, out=wav)
 
     el1, prof = ctx.timed(step, steps, warmup, eng)
+    if args.workload == "full":  # (as the headline; the forms timed below write the same waveform)
+        dump_outputs(ctx, args, wav=wav)
     mel, mel_lens = eng.acoustic(tok, tl, T)
     torch.cuda.synchronize()
     assert int(mel_lens.min()) == T, "forced durations must give 864 frames"
@@ -718,16 +757,16 @@ def main():
             "algorithmic_tflops_per_gpu": round(v["algorithmic_tflops_per_gpu"], 2),
             "roofline": v["roofline"],
         }
-        if not args.no_full:
+        if args.full and not args.no_full:
             out["full_pipeline"] = bench_full(ctx, args, steps=max(3, args.steps // 2), warmup=1)
-        if not args.no_c4:
+        if args.full and not args.no_c4:
             out["c4"] = bench_c4(ctx, args, steps=max(2, args.steps // 3), warmup=1)
-        if not args.no_streaming and ctx.rank == 0:
+        if args.full and not args.no_streaming and ctx.rank == 0:
             out["streaming"] = bench_streaming(ctx)
             for key, kw in (("given_durations", dict(predicted=False)), ("fast_encoder", dict(encoder_precision="fast"))):
                 r = bench_streaming(ctx, **kw)
                 out["streaming"][key] = {k: r[k] for k in ("p50_first_audio_ms", "p90_first_audio_ms")}
-        if not args.no_c1 and ctx.rank == 0 and ctx.world == 1:
+        if args.full and not args.no_c1 and ctx.rank == 0 and ctx.world == 1:
             out["c1"] = bench_c1(ctx)
     else:
         f = bench_full(ctx, args, args.steps, args.warmup)
@@ -741,7 +780,7 @@ def main():
                "per_gpu_samples_per_s": round(per_gpu, 1), "x_realtime_per_gpu": round(per_gpu / SR, 2),
                "rtf": round(SR / per_gpu, 7), "acoustic_ms_per_step": f["acoustic_ms_per_step"],
                "roofline": f["roofline"]}
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline and args.workload != "selftest":
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline and args.workload != "selftest":
         out["cpu_baseline"] = cpu_baseline(args.cpu_c2_batch, args.cpu_c3_batch)  # rank 0 at N=1 only
     if ctx.rank == 0:
         print(json.dumps(out), flush=True)

@@ -60,6 +60,32 @@ def test_failed_rank_ends_the_run_within_seconds():
     assert took < 60, took
 
 
+def _parse(monkeypatch, argv):
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.remove(ROOT)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    return bench.parse()
+
+
+def test_side_measurements_are_off_without_full(monkeypatch):
+    """A plain run measures the headline alone: `--full` is off by default, and the switches that
+    skip single parts of a full run are still accepted beside it."""
+    a = _parse(monkeypatch, ["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (5, 2)
+    a = _parse(monkeypatch, ["--full", "--no-full", "--no-c4", "--dump-outputs", "d"])
+    assert a.full is True and a.no_full is True and a.no_c4 is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_refused_where_nothing_is_dumped(monkeypatch, capsys):
+    with pytest.raises(SystemExit) as e:
+        _parse(monkeypatch, ["--workload", "selftest", "--dump-outputs", "d"])
+    assert e.value.code == 2
+    assert "--dump-outputs" in capsys.readouterr().err
+
+
 def test_driver_torchrun_form_8_ranks():
     """The driver's N=8 launch, verbatim (torch.distributed.run, one node, 8 processes, master on
     127.0.0.1), on the gloo selftest: one JSON line from rank 0 with every rank in the all-reduce."""

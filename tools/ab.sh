@@ -34,9 +34,9 @@ for rep in $(seq 1 $REPS); do
     case $W in
       c2) run_arm "$arm" $lbl python3 $R/bench.py --no-full --no-c4 --no-streaming --no-cpu-baseline --no-c1 || exit 1
           python3 -c "import json; d=json.load(open('$O/$lbl.out')); k=d['roofline']['kernels']; print('$arm', $rep, 'C2', d['ms_per_step'], {a: b['ms_per_step'] for a, b in k.items()})";;
-      c3) run_arm "$arm" $lbl python3 $R/bench.py --no-c4 --no-streaming --no-cpu-baseline --no-c1 || exit 1
+      c3) run_arm "$arm" $lbl python3 $R/bench.py --full --no-c4 --no-streaming --no-cpu-baseline --no-c1 || exit 1
           python3 -c "import json; d=json.load(open('$O/$lbl.out')); f=d['full_pipeline']; print('$arm', $rep, 'C2', d['ms_per_step'], 'C3', f['ms_per_step'], 'acoustic', f['acoustic_ms_per_step'])";;
-      c5) run_arm "$arm" $lbl python3 $R/bench.py --steps 3 --warmup 1 --no-full --no-c4 --no-cpu-baseline --no-c1 || exit 1
+      c5) run_arm "$arm" $lbl python3 $R/bench.py --full --steps 3 --warmup 1 --no-full --no-c4 --no-cpu-baseline --no-c1 || exit 1
           python3 -c "import json; d=json.load(open('$O/$lbl.out')); s=d['streaming']; print('$arm', $rep, 'C5', {k: v for k, v in s.items() if 'ms' in k and not isinstance(v, (list, dict))})";;
       c1) run_arm "$arm" $lbl python3 $R/tools/c1_prof.py || exit 1
           echo "$arm $rep $(tail -1 $O/$lbl.out)";;
