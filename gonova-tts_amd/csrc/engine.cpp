@@ -63,6 +63,7 @@ static bool mrf_chain_enabled() { return sw(SW_MRF_CHAIN) != 0; }
 static bool post_fuse_enabled() { return sw(SW_POST_FUSE) != 0; }
 // streaming upsampler for the small stages (default on; TTS_UP_STREAM=0: conv_xres)
 static bool up_stream_enabled() { return sw(SW_UP_STREAM) != 0; }
+static bool up_fuse_enabled() { return sw(SW_UP_FUSE) != 0; }
 
 struct tts_engine {
   int device = 0;
@@ -444,13 +445,16 @@ struct tts_engine {
     // loads it as is, so the X-resident upsamplers can stage it by LDS-DMA
     bool s_act = true;
     bool post_done = false;  // conv_post ran inside the last pair launch
+    bool up_done = false;    // this stage's upsampler ran inside the previous stage's last pair launch (XS is written)
     for (int i = 0; i < nst; ++i) {
       const int ch = v.stage_ch[i];
       const int Tout = Tin * v.up_rate[i];
       const long long sb = (long long)Tout * ch;
       // lrelu -> ConvTranspose1d (polyphase)
       const ConvLayer& U = v.ups[i];
-      if (U.wup16 && up_stream_enabled()) {
+      if (up_done) {
+        up_done = false;
+      } else if (U.wup16 && up_stream_enabled()) {
         UpsampleParams up{};
         up.x = S; up.sxb = (long long)Tin * cin; up.len = Lp(i); up.up_len = Lp(i + 1);
         up.wpk = U.wup16; up.bias = U.bias; up.y = XS; up.syb = sb;
@@ -552,11 +556,22 @@ struct tts_engine {
               pp.wav = wav; pp.swb = swb;
               post_done = true;
             }
-            const double fl = 2.0 * 2.0 * ch * (double)ch * pp.k * (double)B * Tout;
+            double fl = 2.0 * 2.0 * ch * (double)ch * pp.k * (double)B * Tout;
             // the stage's final MRF sum feeds only the next upsampler: store it activated
             if (last && j == nk - 1 && i + 1 < nst && !pp.post_wpk && mrf_pair_outact_supported(dt, ch, pp.k)) {
               pp.out_act = 1; pp.out_slope = slope;
               s_act = true;
+              // ... or, on full-height tiles, run that upsampler in this launch: XS (last read by the
+              // third resblock's first pair) receives the next stage's x, S is only read
+              const ConvLayer& N = v.ups[i + 1];
+              if (N.wup16 && up_stream_enabled() && up_fuse_enabled() && N.Cin == ch && N.M == ch && N.taps == 2 &&
+                  pp.x != XS && mrf_pair_up_supported(dt, ch, pp)) {
+                pp.up_wpk = N.wup16; pp.up_bias = N.bias; pp.up_y = XS;
+                pp.up_syb = (long long)Tout * v.up_rate[i + 1] * v.stage_ch[i + 1];
+                pp.up_len = Lp(i + 2); pp.up_s = N.up_s; pp.up_co = N.up_cout; pp.up_pad = N.up_p;
+                fl += 2.0 * N.M * (double)N.Cin * N.taps * (double)B * Tout;  // the upsample launch's count
+                up_done = true;
+              }
             }
             auto launch = [&] { return mrf_pair_launch(dt, ch, pp, s); };
             if (prof.on) {

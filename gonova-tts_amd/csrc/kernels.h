@@ -141,9 +141,23 @@ struct MrfPairParams {
   // optional [B][T][C] scratch (compute dtype): with it, launches whose full-height grid is small
   // (the streamed vocoder's first chunk) run the channel-split form (mrf_pair.hip), bit-identical
   void* tbuf;
+  // the next stage's two-tap upsampler fused into a stage's last pair (up_wpk != null; needs
+  // out_act, accepted where mrf_pair_up_supported says so): instead of y = lrelu(S) the launch
+  // writes up_y [B][T*up_s][up_co], the rows upsample_stream_launch would write from that S
+  // (UpsampleParams with slope 1: wpk, bias, y, syb, up_len, s, co, pad), bit-identical.  y is
+  // then only read (accum).
+  const void* up_wpk;    // [C/16][2*C/32][64][8] (frag_pack_up16), M = C outputs per input row
+  const float* up_bias;  // fp32 [C]
+  void* up_y;
+  long long up_syb;
+  const int* up_len;
+  int up_s, up_co, up_pad;
 };
 bool mrf_pair_supported(int dtype, int C, int k);
 bool mrf_pair_outact_supported(int dtype, int C, int k);  // the launch can carry out_act
+// the launch (T, B, k, tbuf set) would run on full-height tiles of a shape compiled with the
+// upsampler fusion (k = 11 at C = 64 / 128), so it can carry up_wpk for a C -> C two-tap upsampler
+bool mrf_pair_up_supported(int dtype, int C, const MrfPairParams& p);
 
 // Streaming ConvTranspose1d with two taps (k = 2s) for the small upsamplers (upsample.hip):
 // x [B][T][Cin] (len[b] valid rows) -> y [B][T*s][Co], rows s*u + r - pad for u = 0 .. len,

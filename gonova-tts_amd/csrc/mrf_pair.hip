@@ -10,9 +10,10 @@
 // in LDS ("G"), computes conv1 for the BN + 2*a2 rows conv2 needs, writes t over G ("T",
 // after a barrier: both tiles at once would not leave 3 blocks per CU), runs conv2 for
 // the BN output rows, stages the output tile in LDS and leaves through 16-byte row pieces,
-// adding the residual h from the input rows (L2-hot: the block just staged them) and, for
-// the last pair of a resblock, the running MRF sum.  HBM traffic per pair: read h once
-// (+ halo, mostly L2), write h' once (S: read + write).
+// adding the residual h from the input rows (re-read from HBM: by the end of conv2 they have
+// left the 4 MB L2, the launch FETCHes 1.48x its algorithmic bytes, profiles/r05o_ab_resreg.txt)
+// and, for the last pair of a resblock, the running MRF sum.  HBM traffic per pair: read h
+// twice (+ halo, mostly L2), write h' once (S: read + write).
 //
 // Why pairs, not whole stages (round 1's mrf_fused kernel, removed) or single convs (conv_xres): a whole-stage
 // tile must carry the receptive-field halo of all three pairs of a resblock (60 rows per
@@ -70,6 +71,10 @@ __device__ unsigned long long g_pair_stamp[1 << 21];
 // conv_post fused into the vocoder's last pair (POST): the block computes PAIR_PO extra output
 // rows per side so conv_post's halo (post_k <= 2*PAIR_PO + 1 taps) is in the block
 constexpr int PAIR_PO = 8;
+// the next stage's 2-tap upsampler fused into a stage's last pair (UP): input row u of the
+// upsampler reads the final-sum rows u - 1 and u, so the block computes PAIR_UPL extra output
+// row before its first
+constexpr int PAIR_UPL = 1;
 
 // Short-tile geometry: BN / DIV output rows per block, everything else as PairGeom<C>.  The
 // launcher picks it when the full-height grid leaves most CUs idle (the streamed vocoder's
@@ -153,11 +158,13 @@ constexpr int pair_bn() {
 #ifndef TTS_PAIR_RESREG_OCC
 #define TTS_PAIR_RESREG_OCC 2    // blocks per CU the RESREG register budget is sized for
 #endif
-template <int C, int DIV, int K = 0, bool POST = false>
+template <int C, int DIV, int K = 0, bool POST = false, bool UP = false>
 struct PairGeomS : PairGeom<C> {
   static constexpr bool RESREG = TTS_PAIR_RESREG && C <= 128 && !POST &&
                                  (TTS_PAIR_RESREG_ONLYC == 0 || C == TTS_PAIR_RESREG_ONLYC);
-  static constexpr int BN = DIV == 1 && K > 0 && !POST ? pair_bn<C, K>() : PairGeom<C>::BN / DIV;
+  // UP: one output row fewer, so the extra final-sum row the fused upsampler needs (PAIR_UPL) adds
+  // no 16-row tile to either conv
+  static constexpr int BN = DIV == 1 && K > 0 && !POST ? pair_bn<C, K>() - (UP ? PAIR_UPL : 0) : PairGeom<C>::BN / DIV;
   // short tiles do few MFMAs per k-step (one row tile per wave), so the weight ring's L2 round
   // trips are exposed unless it runs further ahead; the depth only moves loads earlier (same
   // k-step order: bit-identical).  C = 256, D 2 -> 4 (profiles/r04t_ab_short_ring.txt): the C5
@@ -175,11 +182,11 @@ struct PairGeomS : PairGeom<C> {
 
 // LDS bytes of one launch (G tile incl. conv1 overrun rows, T tile; >= output staging tile of
 // 16 * NT2 rows: conv2's last tile may run past the BO output rows)
-template <int C, int DIV = 1, int K = 0, bool POST = false>
+template <int C, int DIV = 1, int K = 0, bool POST = false, bool UP = false>
 static size_t pair_lds_bytes(int k, int d, bool post) {
-  using G = PairGeomS<C, DIV, K, POST>;
+  using G = PairGeomS<C, DIV, K, POST, UP>;
   const int a1 = (k - 1) / 2 * d, a2 = (k - 1) / 2;
-  const int bo = G::BN + (post ? 2 * PAIR_PO : 0);
+  const int bo = G::BN + (post ? 2 * PAIR_PO : 0) + (UP ? PAIR_UPL : 0);
   const int nt1 = (bo + 2 * a2 + 15) / 16;
   const int nt2 = (bo + 15) / 16;
 
@@ -190,10 +197,18 @@ static size_t pair_lds_bytes(int k, int d, bool post) {
 
 // OUTACT: the stored rows are LeakyReLU(p.out_slope) of the row pass's values (a stage's last
 // pair, whose MRF sum only the next upsampler reads; MrfPairParams::out_act)
-template <typename T, int C, int K, bool POST = false, int DIV = 1, bool OUTACT = false>
-__global__ __launch_bounds__((64 * PairGeom<C>::WM * PairGeom<C>::WN), (PairGeomS<C, DIV, K, POST>::OCC)) void mrf_pair_kernel(
+//
+// UP (with OUTACT, full-height tiles only): the next stage's 2-tap ConvTranspose1d
+// (upsample_stream_kernel's GEMM: per input row u, [g[u-1], g[u]] x W' -> the M = C outputs of
+// rows s*u - pad ..) runs in the block as a third conv over the final rows g = lrelu(S), which
+// never leave the chip: the launch writes the next stage's x (MrfPairParams::up_y) instead of S.
+// Same k-step order (tap 0 channels ascending, then tap 1), zero-initialised accumulators, fp32
+// bias add and one rounding as upsample_stream_kernel: bit-identical to the two launches.
+template <typename T, int C, int K, bool POST = false, int DIV = 1, bool OUTACT = false, bool UP = false>
+__global__ __launch_bounds__((64 * PairGeom<C>::WM * PairGeom<C>::WN), (PairGeomS<C, DIV, K, POST, UP>::OCC)) void mrf_pair_kernel(
     MrfPairParams p) {
-  using G = PairGeomS<C, DIV, K, POST>;
+  using G = PairGeomS<C, DIV, K, POST, UP>;
+  static_assert(!UP || (OUTACT && !POST && DIV == 1 && !G::RESREG), "upsampler fusion: a stage's last pair on full-height tiles");
   typedef typename Mfma<T>::frag Frag;
   constexpr int BN = G::BN, WM = G::WM, WN = G::WN, RS = G::RS;
   constexpr int D = G::D;              // weight ring depth (k-steps)
@@ -203,8 +218,8 @@ __global__ __launch_bounds__((64 * PairGeom<C>::WM * PairGeom<C>::WN), (PairGeom
   constexpr int MT = G::MT;            // 16-channel M tiles per wave
   constexpr int S = K * KS;            // k-steps per conv
   constexpr int A2 = (K - 1) / 2;
-  constexpr int PO = POST ? PAIR_PO : 0;  // extra output rows per side (conv_post's halo)
-  constexpr int BO = BN + 2 * PO;      // output rows: block row o <-> utterance row n0 - PO + o
+  constexpr int PO = POST ? PAIR_PO : UP ? PAIR_UPL : 0;  // extra output rows before the block's first (conv_post's halo, the upsampler's row u - 1)
+  constexpr int BO = BN + PO + (POST ? PAIR_PO : 0);  // output rows: block row o <-> utterance row n0 - PO + o
   constexpr int RT = BO + 2 * A2;      // conv1 rows conv2 needs
   constexpr int NT1 = (RT + 15) / 16;  // conv1 tiles (block)
   constexpr int NU1 = (NT1 + WN - 1) / WN;  // conv1 tiles per wave (the last may be a repeat)
@@ -228,11 +243,13 @@ __global__ __launch_bounds__((64 * PairGeom<C>::WM * PairGeom<C>::WN), (PairGeom
 #define TTS_PSTAMP(i_) (void)0
 #endif
   int b, tile0;
-  if (!xcd_tile((p.T + BN - 1) / BN, p.B, b, tile0)) return;
+  // UP: the upsampler's input rows run to u = len (its polyphase "+1" row, from g[len-1] alone),
+  // so the tiles cover rows 0 .. T and the tile that holds row len still runs
+  if (!xcd_tile(UP ? p.T / BN + 1 : (p.T + BN - 1) / BN, p.B, b, tile0)) return;
   const int n0 = tile0 * BN;
   const int len = min(p.len[b], p.T);
   const int tid = threadIdx.x;
-  if (n0 >= len) {
+  if (UP ? (n0 > len || len <= 0) : n0 >= len) {
     if constexpr (POST) {  // conv_post's grid covered every row: zeros past the utterance
       if (n0 + tid < p.T) p.wav[b * p.swb + n0 + tid] = 0.f;
       if (n0 + tid + 256 < p.T) p.wav[b * p.swb + n0 + tid + 256] = 0.f;
@@ -452,6 +469,94 @@ __global__ __launch_bounds__((64 * PairGeom<C>::WM * PairGeom<C>::WN), (PairGeom
     float* wv = p.wav + b * p.swb;
     if (ta < p.T) wv[ta] = ta < len ? tanhf(acc0) : 0.f;
     if (tb < p.T) wv[tb] = tb < len ? tanhf(acc1) : 0.f;
+    return;
+  }
+  if constexpr (UP) {
+    // the thread's indices afresh: values the compiler would otherwise keep (or spill) across both
+    // convs for this tail
+    int tu = tid;
+    asm volatile("" : "+v"(tu));
+    const int l15u = tu & 15, lqu = (tu & 63) >> 4;
+    const int ch0u = 16 * MT * wm + 4 * lqu;
+    // the upsampler's weights [C/16][2][KS][64][8] (frag_pack_up16: frag_pack16's order with
+    // k = 2) through the ring conv2 is done with, issued after the row pass (before it: no faster,
+    // profiles/upfuse_ab_prefetch_c2.txt)
+    constexpr int S3 = 2 * KS;
+    constexpr int NT3 = (BN + 15) / 16;        // conv3 tiles: tile row j <-> upsampler input row u = n0 + j
+    constexpr int NU3 = (NT3 + WN - 1) / WN;
+    static_assert(NT3 <= NT2 && 16 * NT3 + 1 <= 16 * NT1 + 2 * A2, "conv3's tiles inside the staging tile, its overrun rows inside the G region");
+    const char* w3 = reinterpret_cast<const char*>(p.up_wpk) + (long long)(MT * wm) * S3 * 1024 + (tu & 63) * 16;
+    // final MRF-sum rows exactly as the OUTACT row pass stores them (rounded to T, LeakyReLU'd;
+    // zero outside the utterance, as the upsampler's descriptor reads them) -> the block's tile
+    // in the swizzled PairGeom layout: G row o <-> utterance row n0 - PO + o
+    uint4 gv[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int idx = tu + it * NTHR;
+      const int o = min(idx / VPR, BO - 1), c8 = idx % VPR;
+      const int gr = n0 - PO + o;
+      const uint4 y = *reinterpret_cast<const uint4*>(smem + o * YS16 + c8 * 16);
+      const uint4 v = lrelu_unit<T>(epi_row<T>(y, xin[it], p.accum, sin[it], p.scale), p.out_slope);
+      gv[it] = (gr >= 0 && gr < len) ? v : uint4{0u, 0u, 0u, 0u};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+      if (i < S3)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) ring[i][mt] = *reinterpret_cast<const Frag*>(w3 + ((long long)mt * S3 + i) * 1024);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();  // output staging no longer read
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int idx = tu + it * NTHR;
+      const int o = idx / VPR, c8 = idx % VPR;
+      if (BO * VPR % NTHR == 0 || idx < BO * VPR) *reinterpret_cast<uint4*>(Gs + o * RS + (c8 ^ swz(o)) * 16) = gv[it];
+    }
+    f32x4 bias3[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) bias3[mt] = *reinterpret_cast<const f32x4*>(p.up_bias + ch0u + 16 * mt);
+    __syncthreads();
+    // ---- conv3: tap 0 <-> G row j (utterance row u - 1), tap 1 <-> G row j + 1 (row u) ----
+    f32x4 acc3[NU3][MT];
+#pragma unroll
+    for (int u = 0; u < NU3; ++u)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) acc3[u][mt] = f32x4{};
+    pair_conv<T, C, S3, NU3, D, MT, (C >= TTS_PAIR_MTO_MIN), 16 * WN * RS>(acc3, ring, w3, Gs + (16 * wn + l15u) * RS, RS, 1,
+                                                                           l15u, lqu, last_off(NT3, NU3));
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();  // G no longer read
+    {
+      char* ob = smem + (16 * wn + l15u) * YS16 + ch0u * 2;
+#pragma unroll
+      for (int u = 0; u < NU3; ++u)
+        if (NT3 % WN == 0 || wn + WN * u < NT3) {
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt)  // fp32 bias add, one rounding (as upsample_stream_kernel)
+            *reinterpret_cast<uint2*>(ob + u * 16 * WN * YS16 + 32 * mt) = pack4<T>(acc3[u][mt] + bias3[mt]);
+        }
+    }
+    __syncthreads();
+    // input row u's C outputs are the contiguous bytes of output rows s*u - pad .. (stride co),
+    // under upsample_stream_kernel's bounds: u <= len, 0 <= orow < up_len
+    const int tlen = min(p.up_len[b], p.T * p.up_s);
+    T* yb = reinterpret_cast<T*>(p.up_y) + (long long)b * p.up_syb;
+    constexpr int NIT3 = (BN * VPR + NTHR - 1) / NTHR;
+    int tv = tu;
+    asm volatile("" : "+v"(tv));  // (as tu: the row pass's piece offsets are not held across conv3)
+    // a thread's pieces share their 16-byte column (NTHR % VPR == 0), hence its output phase
+    const int c8 = tv % VPR, m0 = c8 * 8, ph = m0 / p.up_co;
+    const int colb = (m0 - ph * p.up_co) * (int)sizeof(T);
+#pragma unroll
+    for (int it = 0; it < NIT3; ++it) {
+      const int j = tv / VPR + it * (NTHR / VPR);
+      const int u = n0 + j;
+      const int orow = p.up_s * u + ph - p.up_pad;
+      if ((BN * VPR % NTHR != 0 && j >= BN) || u > len || orow < 0 || orow >= tlen) continue;
+      const uint4 v = *reinterpret_cast<const uint4*>(smem + j * YS16 + c8 * 16);
+      store16<2>(yb, (int)((long long)orow * p.up_co * (long long)sizeof(T)) + colb, v);
+    }
     return;
   }
 #pragma unroll
@@ -677,9 +782,31 @@ static bool pair_split(int C, const MrfPairParams& p) {
 template <int C, int K>
 constexpr bool pair_outact_compiled() { return K == 11 && (C == 64 || C == 128 || C == 256); }
 
+// upsampler fusion compiled for the stage-final pairs an in-LDS upsampler follows (HiFi-GAN V1
+// stages 1 and 2: k = 11 at C = 128 / 64)
+#ifndef TTS_PAIR_UP_C128
+#define TTS_PAIR_UP_C128 1  // A/B builds: 0 leaves the stage-2 upsampler (after the C = 128 stage) its own launch
+#endif
+#ifndef TTS_PAIR_UP_C64
+#define TTS_PAIR_UP_C64 1   // A/B builds: 0 leaves the stage-3 upsampler (after the C = 64 stage) its own launch
+#endif
+template <int C, int K>
+constexpr bool pair_up_compiled() { return K == 11 && ((TTS_PAIR_UP_C64 && C == 64) || (TTS_PAIR_UP_C128 && C == 128)); }
+
 template <typename T, int C, int K, bool POST, int DIV>
 static hipError_t launch_pair_g(const MrfPairParams& p, hipStream_t s) {
   using G = PairGeomS<C, DIV, K, POST>;
+  if (p.up_wpk) {
+    if constexpr (!POST && DIV == 1 && pair_up_compiled<C, K>()) {
+      using GU = PairGeomS<C, 1, K, false, true>;
+      const size_t ldsu = pair_lds_bytes<C, 1, K, false, true>(K, p.d, false);
+      if (ldsu > 160 * 1024 || !p.out_act) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((mrf_pair_kernel<T, C, K, false, 1, true, true>), dim3(xcd_grid(p.T / GU::BN + 1, p.B)),
+                         dim3(64 * GU::WM * GU::WN), ldsu, s, p);
+      return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
+  }
   const size_t lds = pair_lds_bytes<C, DIV, K, POST>(K, p.d, POST);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   dim3 grid(xcd_grid((p.T + G::BN - 1) / G::BN, p.B));
@@ -729,6 +856,12 @@ bool mrf_pair_outact_supported(int dtype, int C, int k) {
   return mrf_pair_supported(dtype, C, k) && k == 11 && (C == 64 || C == 128 || C == 256);
 }
 
+bool mrf_pair_up_supported(int dtype, int C, const MrfPairParams& p) {
+  return mrf_pair_outact_supported(dtype, C, p.k) && (C == 64 ? pair_up_compiled<64, 11>() : C == 128 && pair_up_compiled<128, 11>()) &&
+         !p.post_wpk && !pair_split(C, p) &&
+         pair_div(C, p, false) == 1;
+}
+
 bool mrf_pair_post_supported(int dtype, int C, int post_k) {
   return (dtype == DT_F16 || dtype == DT_BF16) && C == 32 && post_k >= 1 && post_k % 2 == 1 &&
          post_k <= 2 * PAIR_PO + 1;
@@ -739,6 +872,9 @@ hipError_t mrf_pair_launch(int dtype, int C, const MrfPairParams& p, hipStream_t
   if (!(p.slope >= 0.f && p.slope <= 1.f)) return hipErrorInvalidValue;  // lrelu_unit / epi_conv1
   if (p.out_act && (!(p.out_slope >= 0.f && p.out_slope <= 1.f) || p.post_wpk)) return hipErrorInvalidValue;
   if (p.post_wpk && !(p.post_slope >= 0.f && p.post_slope <= 1.f)) return hipErrorInvalidValue;
+  if (p.up_wpk && (!mrf_pair_up_supported(dtype, C, p) || !p.out_act || !p.up_bias || !p.up_y || !p.up_len || p.up_s < 1 ||
+                   C % p.up_s || p.up_co != C / p.up_s || p.up_co % 8))
+    return hipErrorInvalidValue;
   if (p.post_wpk) {
     if (!mrf_pair_post_supported(dtype, C, p.post_k) || !p.wav) return hipErrorInvalidValue;
     return dtype == DT_F16 ? launch_pair_k<half_t, 32, true>(p, s) : launch_pair_k<bf16_t, 32, true>(p, s);

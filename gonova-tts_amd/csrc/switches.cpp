@@ -16,7 +16,7 @@ const char* const kNames[SW_N] = {"TTS_REL_ATTN", "TTS_MRF_FUSED", "TTS_MRF_CHAI
                                   "TTS_SPLIT_NT1", "TTS_XRES_ORDER",
                                   "TTS_PAIR_SPLIT", "TTS_VP_BATCH", "TTS_DEC_TRIM", "TTS_ATTN_F32_KC",
                                   "TTS_F32_ENC_SPLIT", "TTS_F32_DEC_SPLIT",
-                                  "TTS_F32_DEC_PACKED"};
+                                  "TTS_F32_DEC_PACKED", "TTS_UP_FUSE"};
 std::atomic<int> g_val[SW_N];
 std::once_flag g_once;
 

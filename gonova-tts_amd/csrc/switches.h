@@ -28,6 +28,7 @@ enum Sw : int {
   SW_F32_ENC_SPLIT,  // TTS_F32_ENC_SPLIT=0: an fp32 model's encoder side on fp32 MFMA even with TTS_ENCODER_EXACT (read at finalize)
   SW_F32_DEC_SPLIT,  // TTS_F32_DEC_SPLIT=0: an fp32 model's decoder / postnet all on fp32 MFMA (read at finalize; needs the encoder split)
   SW_F32_DEC_PACKED,  // TTS_F32_DEC_PACKED=0: the fp32 decoder's FFN down-projections on fp32 MFMA, not the packed split-K form (finalize)
+  SW_UP_FUSE,      // TTS_UP_FUSE=0: stages 2-3 upsamplers as their own launches, not inside the preceding stage's last pair
   SW_N
 };
 

@@ -70,17 +70,26 @@ def per_dispatch(path, counter):
 CHAIN = {(32, 3), (32, 7), (64, 3)}   # (C, k) resblocks run as one chain launch (mrf_chain.hip)
 
 
-def step_launches(B, T, elt=2, pair_channels=(32, 64, 128, 256), chain=CHAIN, post_fused=True):
+UP_FUSED = ("s2.up", "s3.up")   # upsamplers run inside the preceding stage's last pair launch (mrf_pair.hip, UP)
+
+
+def step_launches(B, T, elt=2, pair_channels=(32, 64, 128, 256), chain=CHAIN, post_fused=True, up_fused=UP_FUSED):
     """[(label, algorithmic bytes, algorithmic FLOPs)] of one default-path step, in launch
     order: single convs for stages whose width has no pair kernel, one chain launch per
     resblock in `chain`, ResBlock-pair launches otherwise; conv_post inside the last pair
-    launch when `post_fused` (the final MRF sum is not written, the waveform is)."""
+    launch when `post_fused` (the final MRF sum is not written, the waveform is); the upsamplers
+    in `up_fused` inside the preceding stage's last pair launch (labelled "+up": the MRF sum is
+    not written, the next stage's x is -- the same bytes -- and the upsampler's weights and FLOPs
+    are added)."""
     out = []
     npairs = {}
     for name, M, cin, k, n in vocoder_layers(T):
         st = name.split(".")[0]
         f = 2.0 * M * cin * k * n * B
-        if name == "post" and post_fused and out and ".pair" in out[-1][0]:
+        if name in up_fused and out and ".pair" in out[-1][0]:
+            lab, by, fl = out[-1]
+            out[-1] = (lab + "+up", by - B * n * cin * elt + B * n * M * elt + M * cin * k * elt, fl + f)
+        elif name == "post" and post_fused and out and ".pair" in out[-1][0]:
             lab, by, fl = out[-1]
             out[-1] = (lab + "+post", by - B * n * cin * elt + B * n * 4, fl + f)
         elif name == "post":

@@ -1,7 +1,9 @@
 """Per-launch / per-stage breakdown of the last default-path vocoder step from a rocprofv3
 kernel trace (bench.py --no-full --no-streaming ...; tools/prof_fused.sh).
 
-usage: python tools/step_breakdown.py gpurun_out/<dir>/run_kernel_trace.csv [B T]
+usage: python tools/step_breakdown.py <trace dir>/run_kernel_trace.csv [B T] [--separate-up]
+(--separate-up: the trace of a run with TTS_UP_FUSE=0, or of a library from before the stage 2-3
+upsamplers moved into the preceding pair launches: "s2.up" / "s3.up" are launches of their own)
 Labels come from tools/pmc_traffic.fused_step_layers (pre, ups, stage-0 convs, ResBlock
 pairs, post); FLOPs are algorithmic (2*M*Cin*k per produced row; a pair counts both convs).
 """
@@ -15,12 +17,13 @@ from tools.pmc_traffic import family, step_launches  # noqa: E402
 
 
 def main():
-    path = sys.argv[1]
-    B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
-    T = int(sys.argv[3]) if len(sys.argv) > 3 else 862
+    argv = [a for a in sys.argv if a != "--separate-up"]
+    path = argv[1]
+    B = int(argv[2]) if len(argv) > 2 else 32
+    T = int(argv[3]) if len(argv) > 3 else 862
     rows = [r for r in csv.DictReader(open(path)) if family(r["Kernel_Name"])]
     rows.sort(key=lambda r: int(r["Dispatch_Id"]))
-    step = step_launches(B, T)
+    step = step_launches(B, T, up_fused=()) if "--separate-up" in sys.argv else step_launches(B, T)
     rows = rows[-len(step):]
     stage = OrderedDict()
     total = 0.0
