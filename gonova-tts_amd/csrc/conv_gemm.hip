@@ -37,7 +37,7 @@
 
 namespace tts {
 
-constexpr int HALO_MAX = 64;  // max (taps-1)*dil supported (HiFi-GAN V1: 50)
+constexpr int HALO_MAX = CONV_HALO_MAX;  // max (taps-1)*dil supported (HiFi-GAN V1: 50)
 
 template <typename T>
 __device__ inline uint4 act16(uint4 u, bool valid, float slope) {

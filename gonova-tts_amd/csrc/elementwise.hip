@@ -37,23 +37,25 @@ hipError_t launch_mel_in(int dtype, const float* mel, long long smb, int smr, co
 
 // out[k*B + b] = in[b] * mult[k] + add[k]  (per-utterance row counts of every stage)
 __global__ void lens_kernel(const int* __restrict__ in, int* __restrict__ out, int B, int4 m0, int4 m1,
-                            int4 a0, int4 a1, int n) {
+                            int4 a0, int4 a1, int n, int cap) {
   const int b = threadIdx.x + blockIdx.x * blockDim.x;
   if (b >= B) return;
-  const int v = in[b];
+  // a length outside [0, cap] (the rows the caller's buffers hold per utterance) is clamped here, so
+  // no launch that bounds its rows by a derived length can leave its utterance's rows
+  const int v = min(max(in[b], 0), cap);
   const int mult[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
   const int add[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
   for (int k = 0; k < n; ++k) out[k * B + b] = v * mult[k] + add[k];
 }
 
-hipError_t launch_lens(const int* in, int* out, int B, const int* mult, const int* add, int n,
+hipError_t launch_lens(const int* in, int* out, int B, const int* mult, const int* add, int n, int cap,
                        hipStream_t s) {
   if (n > 8) return hipErrorInvalidValue;
   int m[8] = {0}, a[8] = {0};
   for (int i = 0; i < n; ++i) { m[i] = mult[i]; a[i] = add[i]; }
   hipLaunchKernelGGL(lens_kernel, dim3((B + 255) / 256), dim3(256), 0, s, in, out, B,
                      make_int4(m[0], m[1], m[2], m[3]), make_int4(m[4], m[5], m[6], m[7]),
-                     make_int4(a[0], a[1], a[2], a[3]), make_int4(a[4], a[5], a[6], a[7]), n);
+                     make_int4(a[0], a[1], a[2], a[3]), make_int4(a[4], a[5], a[6], a[7]), n, cap);
   return hipGetLastError();
 }
 

@@ -82,7 +82,8 @@ struct tts_engine {
   size_t vbuf_elems = 0;
   void* vmel = nullptr;  // normalized mel in compute dtype
   size_t vmel_elems = 0;
-  int* vlens = nullptr;  // [16][max_batch]
+  int* vlens = nullptr;  // [16][max_batch]: rows 0 .. 7 the stage lengths, 8 .. 15 the polyphase row counts
+  static constexpr int VOC_MAX_STAGES = 7;
   int vlens_batch = 0;
   float* vchunk_wav = nullptr;
   size_t vchunk_elems = 0;
@@ -182,7 +183,6 @@ struct tts_engine {
   ConvLayer pack_transposed(const std::string& wname, const std::string& bname, int s, int dt) {
     const HostTensor& w = get(wname);
     const int ci = (int)w.shape[0], co = (int)w.shape[1], k = (int)w.shape[2];
-    if (k % s || (k - s) % 2) throw TtsError(TTS_ERR_INVALID, wname + ": need k % s == 0 and even k-s");
     const int taps = k / s;
     const int M = s * co;
     std::vector<float> p((size_t)M * taps * ci);
@@ -207,8 +207,114 @@ struct tts_engine {
     return L;
   }
 
+  // The supported vocoder envelope, checked from the weight shapes and the
+  // configuration before anything is packed: a configuration passes only if every dtype and every
+  // kernel-path switch can run it, so nothing that loads fails at its first forward.  Each message
+  // names the tensor and the limit.  Returns what it read, which finalize_vocoder packs from.
+  struct VocoderShape {
+    int nst = 0, nk = 0;                 // stages, resblocks per stage
+    std::vector<int> stride;             // [nst]
+    std::vector<std::vector<int>> dil;   // [nst * nk][pairs]: conv1's dilation of each pair
+  };
+  VocoderShape check_vocoder_envelope() {
+    auto bad = [](const std::string& what) { throw TtsError(TTS_ERR_INVALID, "vocoder envelope: " + what); };
+    auto dims = [&](const std::string& n) -> const std::vector<int64_t>& {
+      const HostTensor& t = get(n);
+      if (t.shape.size() != 3) bad(n + ": expected a 3-D conv weight");
+      return t.shape;
+    };
+    // 16-byte rows in every dtype (16-bit: 8 elements)
+    auto ch16 = [&](const std::string& n, int64_t c, const char* which) {
+      if (c <= 0 || c % 8) bad(n + ": " + which + " channel count " + std::to_string(c) +
+                               " is not a multiple of 8 (rows of 16-byte pieces)");
+    };
+    auto halo = [&](const std::string& n, int64_t k, int64_t d) {
+      if (k < 1 || k % 2 == 0) bad(n + ": kernel size " + std::to_string(k) + " is not odd");
+      if ((k - 1) * d > CONV_HALO_MAX)
+        bad(n + ": receptive field (k-1)*dilation = " + std::to_string((k - 1) * d) + " exceeds " +
+            std::to_string(CONV_HALO_MAX) + " rows");
+    };
+    const auto& pre = dims("conv_pre.weight");
+    ch16("conv_pre.weight", pre[1], "input");
+    ch16("conv_pre.weight", pre[0], "output");
+    if (pre[2] != 7) bad("conv_pre.weight: kernel size " + std::to_string(pre[2]) + "; conv_pre is padded for 7 taps");
+    int nst = 0;
+    while (has("upsampler." + std::to_string(nst) + ".weight")) ++nst;
+    int nres = 0;
+    while (has("resblocks." + std::to_string(nres) + ".convs1.0.weight")) ++nres;
+    if (nst == 0 || nres == 0 || nres % nst) bad("resblocks.*: " + std::to_string(nres) + " resblocks do not divide over " +
+                                                 std::to_string(nst) + " upsampler stages");
+    if (nst > VOC_MAX_STAGES) bad("upsampler." + std::to_string(VOC_MAX_STAGES) + ".weight: more than " +
+                                  std::to_string(VOC_MAX_STAGES) + " stages");
+    const int nk = nres / nst;
+    VocoderShape vs;
+    vs.nst = nst; vs.nk = nk;
+    const HostTensor* rates = has("__cfg__.upsample_rates") ? &get("__cfg__.upsample_rates") : nullptr;
+    if (rates && (int)rates->data.size() != nst)
+      bad("__cfg__.upsample_rates: " + std::to_string(rates->data.size()) + " rates for " + std::to_string(nst) + " stages");
+    const HostTensor* dd = has("__cfg__.resblock_dilation_sizes") ? &get("__cfg__.resblock_dilation_sizes") : nullptr;
+    if (dd && (dd->shape.size() != 2 || dd->shape[0] != nk))
+      bad("__cfg__.resblock_dilation_sizes: expected [" + std::to_string(nk) + "][pairs]");
+    int64_t cin = pre[0];
+    for (int i = 0; i < nst; ++i) {
+      const std::string un = "upsampler." + std::to_string(i) + ".weight";
+      const auto& us = dims(un);
+      if (us[0] != cin) bad(un + ": " + std::to_string(us[0]) + " input channels after a layer of " + std::to_string(cin));
+      ch16(un, us[1], "output");
+      const int64_t k = us[2];
+      const int64_t s = rates ? (int64_t)std::lround(rates->data[i]) : k / 2;
+      if (s < 1 || k % s || (k - s) % 2)
+        bad(un + ": kernel " + std::to_string(k) + " with stride " + std::to_string(s) +
+            " (need k % stride == 0 and an even k - stride)");
+      if (k / s - 1 > CONV_HALO_MAX)
+        bad(un + ": " + std::to_string(k / s) + " taps per phase exceed " + std::to_string(CONV_HALO_MAX + 1));
+      vs.stride.push_back((int)s);
+      const std::string ub = "upsampler." + std::to_string(i) + ".bias";
+      if (!has(ub) || (int64_t)get(ub).data.size() != us[1]) bad(ub + ": expected " + std::to_string(us[1]) + " values");
+      const int64_t ch = us[1];
+      for (int j = 0; j < nk; ++j) {
+        const std::string rp = "resblocks." + std::to_string(i * nk + j) + ".";
+        const int64_t ks = dims(rp + "convs1.0.weight")[2];
+        int np = 0;
+        while (has(rp + "convs1." + std::to_string(np) + ".weight")) ++np;
+        if (!dd && np > 3)
+          bad(rp + "convs1.3.weight: more than 3 pairs need __cfg__.resblock_dilation_sizes (the default is 1, 3, 5)");
+        if (dd && dd->shape[1] < np)
+          bad("__cfg__.resblock_dilation_sizes: " + std::to_string(dd->shape[1]) + " dilations for the " +
+              std::to_string(np) + " pairs of " + rp + "convs1");
+        vs.dil.emplace_back();
+        for (int q = 0; q < np; ++q) {
+          const int64_t d = dd ? (int64_t)std::lround(dd->data[(size_t)j * dd->shape[1] + q]) : (q == 0 ? 1 : q == 1 ? 3 : 5);
+          for (int cv = 0; cv < 2; ++cv) {
+            const std::string wn = rp + (cv ? "convs2." : "convs1.") + std::to_string(q) + ".weight";
+            if (!has(wn)) bad(wn + ": missing");
+            const auto& ws = dims(wn);
+            if (ws[0] != ch || ws[1] != ch || ws[2] != ks)
+              bad(wn + ": expected [" + std::to_string(ch) + "][" + std::to_string(ch) + "][" + std::to_string(ks) + "]");
+            if (cv == 0 && d < 1) bad(wn + ": dilation " + std::to_string(d));
+            halo(wn, ks, cv ? 1 : d);
+          }
+          vs.dil.back().push_back((int)d);
+        }
+      }
+      cin = ch;
+    }
+    const auto& ps = dims("conv_post.weight");
+    if (ps[0] != 1 || ps[1] != cin)
+      bad("conv_post.weight: expected [1][" + std::to_string(cin) + "][k] after the last stage");
+    if (ps[1] != CONV_POST_CHANNELS)
+      bad("conv_post.weight: " + std::to_string(ps[1]) + " input channels; the conv_post kernels take a last stage of " +
+          std::to_string(CONV_POST_CHANNELS));
+    // (the conv_post kernels take any odd k and the fused form up to 17 taps, but only the 7 taps
+    // of every HiFi-GAN generator have been run)
+    if (ps[2] != 7) bad("conv_post.weight: kernel size " + std::to_string(ps[2]) + "; conv_post is tested at 7 taps only");
+    return vs;
+  }
+
   void finalize_vocoder() {
     if (!has("conv_pre.weight")) return;
+    const VocoderShape vs = check_vocoder_envelope();
+    const int nst = vs.nst, nk = vs.nk;
     const int dt = cfg.vocoder_dtype;
     VocoderWeights& v = voc;
     v.conv_pre = pack_conv("conv_pre.weight", "conv_pre.bias", 1, 3, dt);
@@ -217,20 +323,11 @@ struct tts_engine {
       v.scale = (float*)track(upload_f32(get("scale").data));
       v.normalize = true;
     }
-    int nst = 0;
-    while (has("upsampler." + std::to_string(nst) + ".weight")) ++nst;
-    int nres = 0;
-    while (has("resblocks." + std::to_string(nres) + ".convs1.0.weight")) ++nres;
-    if (nst == 0 || nres % nst) throw TtsError(TTS_ERR_INVALID, "inconsistent vocoder weights");
-    const int nk = nres / nst;
     v.hop = 1;
     v.ups.clear(); v.up_rate.clear(); v.stage_ch.clear(); v.mrf.assign(nst, {});
     for (int i = 0; i < nst; ++i) {
       const HostTensor& w = get("upsampler." + std::to_string(i) + ".weight");
-      const int k = (int)w.shape[2];
-      // stride from "__cfg__.upsample_rates" if given, else HiFi-GAN V1's k = 2*stride
-      int s = k / 2;
-      if (has("__cfg__.upsample_rates")) s = (int)std::lround(get("__cfg__.upsample_rates").data.at(i));
+      const int s = vs.stride[i];  // "__cfg__.upsample_rates" if given, else HiFi-GAN V1's k = 2*stride
       v.ups.push_back(pack_transposed("upsampler." + std::to_string(i) + ".weight",
                                       "upsampler." + std::to_string(i) + ".bias", s, dt));
       v.up_rate.push_back(s);
@@ -241,15 +338,11 @@ struct tts_engine {
       for (int j = 0; j < nk; ++j) {
         const std::string pre = "resblocks." + std::to_string(i * nk + j) + ".";
         const int ks = (int)get(pre + "convs1.0.weight").shape[2];
-        int np = 0;
-        while (has(pre + "convs1." + std::to_string(np) + ".weight")) ++np;
+        const std::vector<int>& dils = vs.dil[(size_t)i * nk + j];  // the table's, or the default 1, 3, 5
+        const int np = (int)dils.size();
         v.mrf[i][j].resize(np);
         for (int q = 0; q < np; ++q) {
-          int d = q == 0 ? 1 : (q == 1 ? 3 : 5);
-          if (has("__cfg__.resblock_dilation_sizes")) {
-            const HostTensor& dd = get("__cfg__.resblock_dilation_sizes");  // [nk][np]
-            d = (int)std::lround(dd.data.at((size_t)j * dd.shape.at(1) + q));
-          }
+          const int d = dils[q];
           // fp32 vocoders: the wide stages' resblock convs (C >= TTS_VOC_SPLIT_MINC) as split-precision
           // GEMMs -- C1's batch-1 fp32 vocoder ran them on the fp32 MFMA at 15-25 TF/s
           const bool split = dt == DT_F32 && ch >= TTS_VOC_SPLIT_MINC && ch % 32 == 0;
@@ -375,7 +468,7 @@ struct tts_engine {
       p.f32_splitk = 1; p.ws = vws; p.ws_bytes = vws_bytes;
     }
     // algorithmic FLOPs: 2 * Cout * Cin * k per produced row (transposed: per input row, all phases)
-    const double fl = 2.0 * L.M * (double)L.Cin * L.taps * (double)B * (L.up_s ? (y_rows - 1) : y_rows);
+    const double fl = 2.0 * L.M * (double)L.Cin * L.taps * (double)B * (L.up_s ? x_rows : y_rows);
     launch_conv_checked(p, dt, s, &prof, fl);
   }
 
@@ -416,12 +509,16 @@ struct tts_engine {
     int cum = 1;
     mult[n] = 1; add[n] = 0; ++n;  // L0
     for (int i = 0; i < nst; ++i) { cum *= v.up_rate[i]; mult[n] = cum; add[n] = 0; ++n; }
-    if (n > 8) throw TtsError(TTS_ERR_INVALID, "too many stages");
-    HIP_CHECK(launch_lens(mel_lens, vlens, B, mult, add, n, s));
+    if (nst > VOC_MAX_STAGES) throw TtsError(TTS_ERR_INVALID, "too many stages");
+    HIP_CHECK(launch_lens(mel_lens, vlens, B, mult, add, n, T, s));
+    // polyphase rows of upsampler i: input row u writes output rows s*u + r - p (r < s), so the
+    // last output row len*s - 1 needs u up to len + (p - 1) / s: one row past the input for
+    // p <= s (k <= 3 s), more for longer kernels
+    auto up_extra = [&](int i) { return 1 + (v.ups[i].up_p > 0 ? (v.ups[i].up_p - 1) / v.ups[i].up_s : 0); };
     int mult2[8], add2[8];
     cum = 1;
-    for (int i = 0; i < nst; ++i) { mult2[i] = cum; add2[i] = 1; cum *= v.up_rate[i]; }
-    HIP_CHECK(launch_lens(mel_lens, vlens + 8 * B, B, mult2, add2, nst, s));
+    for (int i = 0; i < nst; ++i) { mult2[i] = cum; add2[i] = up_extra(i); cum *= v.up_rate[i]; }
+    HIP_CHECK(launch_lens(mel_lens, vlens + 8 * B, B, mult2, add2, nst, T, s));
     auto Lp = [&](int i) { return vlens + i * B; };
     auto Up = [&](int i) { return vlens + (8 + i) * B; };
 
@@ -470,7 +567,7 @@ struct tts_engine {
           HIP_CHECK(upsample_stream_launch(dt, U.Cin, U.M, up, s));
         }
       } else {
-        run_conv(U, S, (long long)Tin * cin, cin, Lp(i), Tin, XS, sb, ch, Up(i), Tin + 1, s_act ? 1.f : slope, nullptr,
+        run_conv(U, S, (long long)Tin * cin, cin, Lp(i), Tin, XS, sb, ch, Up(i), Tin + up_extra(i), s_act ? 1.f : slope, nullptr,
                  nullptr, 0, 0, 1.f, B, Lp(i + 1), dt, s);
       }
       s_act = false;  // until this stage's final MRF sum says otherwise

@@ -85,6 +85,12 @@ inline ConvParams conv_params_default() {
   return p;
 }
 
+// limits of the conv kernels a model must stay inside (the engine checks them when weights are
+// finalized): the receptive field (taps - 1) * dil of conv_gemm / conv_xres / conv_split, and the
+// channel count launch_conv_post and the fused conv_post of the last pair are written for
+constexpr int CONV_HALO_MAX = 64;
+constexpr int CONV_POST_CHANNELS = 32;
+
 int conv_gemm_check(const ConvParams& p, int dtype, const char** why);
 hipError_t conv_gemm_launch(int dtype, const ConvParams& p, hipStream_t s);
 // kernels the calling thread's last conv_gemm_launch enqueued (the GEMM, a split-K reduce, a LayerNorm)
@@ -206,7 +212,8 @@ hipError_t launch_resample_poly(const float* x, long long sxb, const int* in_len
 // elementwise.hip
 hipError_t launch_mel_in(int dtype, const float* mel, long long smb, int smr, const float* mean,
                          const float* scale, void* out, int B, int T, int C, hipStream_t s);
-hipError_t launch_lens(const int* in, int* out, int B, const int* mult, const int* add, int n,
+// out[k][b] = clamp(in[b], 0, cap) * mult[k] + add[k]
+hipError_t launch_lens(const int* in, int* out, int B, const int* mult, const int* add, int n, int cap,
                        hipStream_t s);
 // wpk (optional, 16-bit dtypes): the same weights [k][C] in the compute dtype -> dot2 kernel
 hipError_t launch_conv_post(int dtype, const void* x, const int* x_len, int B, int T, int C,

@@ -125,7 +125,10 @@ int tts_engine_create_sized(int hip_device, const tts_config* cfg, size_t cfg_si
 /* Host fp32 tensor in HF state_dict naming (e.g. "resblocks.3.convs1.2.weight"). */
 int tts_engine_set_weight(tts_engine* eng, const char* name, const float* host_data,
                           const int64_t* shape, int ndim);
-/* Fold / pack / upload every weight set so far; must precede any forward. */
+/* Fold / pack / upload every weight set so far; must precede any forward.  A vocoder
+ * configuration outside the supported envelope (last stage of 32 channels,
+ * channel counts in multiples of 8, k % stride == 0 with an even k - stride, (k - 1) * dilation
+ * <= 64) is refused here with TTS_ERR_INVALID and a tts_last_error() text naming the tensor. */
 int tts_engine_finalize(tts_engine* eng);
 /* Pre-size the workspace (so later calls allocate nothing and can be graph-captured). */
 int tts_engine_reserve(tts_engine* eng, int max_batch, int max_frames, int max_tokens);
