@@ -943,6 +943,22 @@ int tts_engine_profile_read_kinds(tts_engine* eng, int nkinds, double* ms, doubl
   });
 }
 
+// the engine's polyphase table for a reduced (up, down): designed and uploaded at the pair's first
+// use, cached for the engine's life (later calls allocate nothing)
+static tts_engine::Resampler resampler_for(tts_engine* eng, int up, int down) {
+  for (auto& r : eng->resamplers)
+    if (r.up == up && r.down == down) return r;
+  std::vector<double> h;
+  int npr = 0;
+  const int n = resample_design(up, down, h, npr);
+  const int nq = (n + up - 1) / up;
+  std::vector<float> hp((size_t)up * nq, 0.f);
+  for (int k = 0; k < n; ++k) hp[(size_t)(k % up) * nq + k / up] = (float)h[k];
+  float* d = upload_f32(hp);
+  eng->resamplers.push_back({up, down, nq, npr, d});
+  return eng->resamplers.back();
+}
+
 int tts_resample_filter(int up, int down, double* h, int cap, int* n_pre_remove) {
   try {
     if (up <= 0 || down <= 0) throw TtsError(TTS_ERR_INVALID, "resample: up/down must be positive");
@@ -967,23 +983,54 @@ int tts_resample_poly(tts_engine* eng, const float* d_in, int64_t in_stride, con
       throw TtsError(TTS_ERR_INVALID, "bad resample args");
     const int g = std::gcd(up, down);
     up /= g; down /= g;
-    tts_engine::Resampler* rs = nullptr;
-    for (auto& r : eng->resamplers)
-      if (r.up == up && r.down == down) rs = &r;
-    if (!rs) {
-      std::vector<double> h;
-      int npr = 0;
-      const int n = resample_design(up, down, h, npr);
-      const int nq = (n + up - 1) / up;
-      std::vector<float> hp((size_t)up * nq, 0.f);
-      for (int k = 0; k < n; ++k) hp[(size_t)(k % up) * nq + k / up] = (float)h[k];
-      float* d = upload_f32(hp);
-      eng->resamplers.push_back({up, down, nq, npr, d});
-      rs = &eng->resamplers.back();
-    }
+    const tts_engine::Resampler rs = resampler_for(eng, up, down);
     tts_engine::CallOrder order(eng, (hipStream_t)stream);
-    HIP_CHECK(launch_resample_poly(d_in, in_stride, d_in_lens, B, up, down, rs->nq, rs->n_pre_remove, rs->hp, d_out,
+    HIP_CHECK(launch_resample_poly(d_in, in_stride, d_in_lens, B, up, down, rs.nq, rs.n_pre_remove, rs.hp, d_out,
                                    out_stride, out_cap, d_out_lens, (hipStream_t)stream));
+  });
+}
+
+int tts_resample_history(int up, int down, int* n_hist, int* n_flush) {
+  try {
+    if (up <= 0 || down <= 0) throw TtsError(TTS_ERR_INVALID, "resample: up/down must be positive");
+    const int g = std::gcd(up, down);
+    std::vector<double> hv;
+    int npr = 0;
+    const int n = resample_design(up / g, down / g, hv, npr);
+    if (n_hist) *n_hist = (n + up / g - 1) / (up / g) - 1;
+    if (n_flush) *n_flush = npr;
+    return TTS_OK;
+  } catch (const TtsError& e) {
+    g_last_error = e.what();
+    return e.code;
+  }
+}
+
+int tts_resample_poly_chunk(tts_engine* eng, const float* d_in, int64_t in_stride, int64_t in_start, int in_count,
+                            const int32_t* d_in_lens, int B, int up, int down, const float* d_hist_in,
+                            float* d_hist_out, float* d_out, int64_t out_stride, int out_cap, int32_t* d_out_lens,
+                            void* stream) {
+  return guarded(eng, [&] {
+    if (up <= 0 || down <= 0) throw TtsError(TTS_ERR_INVALID, "resample chunk: up/down must be positive");
+    if (in_start < 0 || in_count < 0)
+      throw TtsError(TTS_ERR_INVALID, "resample chunk: in_start and in_count must be non-negative");
+    if (!d_in || !d_in_lens || !d_out || !d_hist_out || B <= 0 || in_stride < in_count || out_stride < out_cap)
+      throw TtsError(TTS_ERR_INVALID, "bad resample chunk args");
+    if (in_start > 0 && !d_hist_in)
+      throw TtsError(TTS_ERR_INVALID, "resample chunk: a chunk after the first needs d_hist_in");
+    if (d_hist_in == d_hist_out)
+      throw TtsError(TTS_ERR_INVALID, "resample chunk: d_hist_out must not be d_hist_in");
+    const int g = std::gcd(up, down);
+    up /= g; down /= g;
+    const tts_engine::Resampler rs = resampler_for(eng, up, down);
+    const long long need = ((long long)in_count * up + down - 1) / down + rs.n_pre_remove;
+    if (out_cap < need)
+      throw TtsError(TTS_ERR_INVALID, "resample chunk: out_cap " + std::to_string(out_cap) + " below ceil(in_count*up/down)"
+                     " + n_flush = " + std::to_string(need));
+    tts_engine::CallOrder order(eng, (hipStream_t)stream);
+    HIP_CHECK(launch_resample_poly_chunk(d_in, in_stride, in_start, in_count, d_in_lens, B, up, down, rs.nq,
+                                         rs.n_pre_remove, rs.hp, d_hist_in, d_hist_out, d_out, out_stride, out_cap,
+                                         d_out_lens, (hipStream_t)stream));
   });
 }
 

@@ -208,6 +208,12 @@ int resample_design(int up, int down, std::vector<double>& h, int& n_pre_remove)
 hipError_t launch_resample_poly(const float* x, long long sxb, const int* in_lens, int B, int up, int down, int nq,
                                 int n_pre_remove, const float* hp, float* y, long long syb, int y_cap,
                                 int* out_lens, hipStream_t s);
+// one chunk of a stream (samples [in_start, in_start + in_count) in cur, the nq - 1 before them in
+// hist_in): the outputs that are complete with it, their count, and the next chunk's history
+hipError_t launch_resample_poly_chunk(const float* cur, long long sxb, long long in_start, int in_count,
+                                      const int* in_lens, int B, int up, int down, int nq, int n_pre_remove,
+                                      const float* hp, const float* hist_in, float* hist_out, float* y,
+                                      long long syb, int y_cap, int* out_lens, hipStream_t s);
 
 // elementwise.hip
 hipError_t launch_mel_in(int dtype, const float* mel, long long smb, int smr, const float* mean,

@@ -13,8 +13,10 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import os
 import threading
+from math import gcd
 from typing import Dict, Optional
 
 import numpy as np
@@ -83,6 +85,9 @@ C_API = [
                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
     ("tts_resample_poly", _I, [_VP, _VP, ctypes.c_int64, _VP, _I, _I, _I, _VP, ctypes.c_int64, _I, _VP, _VP]),
     ("tts_resample_filter", _I, [_I, _I, ctypes.POINTER(ctypes.c_double), _I, ctypes.POINTER(ctypes.c_int)]),
+    ("tts_resample_poly_chunk", _I, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, _I, _VP, _I, _I, _I, _VP, _VP, _VP,
+                                     ctypes.c_int64, _I, _VP, _VP]),
+    ("tts_resample_history", _I, [_I, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ("tts_set_switch", _I, [ctypes.c_char_p, _I]),
     ("tts_get_switch", _I, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
     ("tts_last_error", ctypes.c_char_p, []),
@@ -126,6 +131,33 @@ def resample_filter(up: int, down: int):
     lib.tts_resample_filter(up, down, h, n, ctypes.byref(npr))
     import numpy as _np
     return _np.frombuffer(h, dtype=_np.float64).copy(), npr.value
+
+
+@functools.lru_cache(maxsize=None)
+def resample_history(up: int, down: int):
+    """Host-side (no GPU): (n_hist, n_flush) of tts_resample_poly_chunk -- the input samples it
+    carries between chunks and the outputs it holds back until an utterance ends."""
+    lib = load_library()
+    h, f = ctypes.c_int(), ctypes.c_int()
+    check(lib.tts_resample_history(up, down, ctypes.byref(h), ctypes.byref(f)), "tts_resample_history")
+    return h.value, f.value
+
+
+def resample_chunk_counts(n_in, in_start: int, in_count: int, up: int, down: int) -> np.ndarray:
+    """Outputs tts_resample_poly_chunk emits for the chunk [in_start, in_start + in_count) of
+    utterances of final lengths n_in (array): the kernel's integer arithmetic on the host, so a
+    streaming caller knows each chunk's valid counts without reading them back.  np.int64 [B]."""
+    g = gcd(up, down)
+    up, down = up // g, down // g
+    n_flush = resample_history(up, down)[1]
+    n_in = np.asarray(n_in, np.int64)
+    n_out = -(-n_in * up // down)
+
+    def emitted(end):
+        return np.where(end >= n_in, n_out, np.clip(-(-end * up // down) - n_flush, 0, n_out))
+
+    lo = emitted(in_start) if in_start else np.zeros_like(n_out)
+    return emitted(in_start + in_count) - lo
 
 
 def device_bytes(device=0) -> int:
@@ -309,6 +341,38 @@ class HipEngine:
                                          ctypes.c_void_p(out.data_ptr()), out.shape[1], cap,
                                          ctypes.c_void_p(out_lens.data_ptr()), _stream_ptr(stream)),
               "tts_resample_poly")
+        return out, out_lens
+
+    def resample_chunk(self, cur, in_start: int, in_lens, up: int, down: int, hist_in, hist_out, in_count=None,
+                       out=None, return_lens: bool = True, stream=None):
+        """One chunk of a resampled stream (tts_resample_poly_chunk): cur cuda float32 [B, S] holds
+        samples [in_start, in_start + in_count) of every utterance (in_count defaults to S), in_lens
+        (cuda int32 [B]) the utterances' final lengths, hist_in / hist_out two distinct cuda float32
+        [B, resample_history(up, down)[0]] buffers (hist_in is not read at in_start == 0; the
+        caller passes this call's hist_out as the next call's hist_in).  -> (out cuda float32
+        [B, ceil(in_count*up/down) + n_flush], out_lens cuda int32 [B], or None with
+        return_lens=False: resample_chunk_counts gives the same counts on the host).  The chunks'
+        outputs, one after another, equal resample() of the whole input bit for bit."""
+        import torch
+        assert cur.is_cuda and cur.dtype == torch.float32 and cur.dim() == 2 and cur.is_contiguous()
+        B, S = cur.shape
+        in_count = S if in_count is None else int(in_count)
+        n_hist, n_flush = resample_history(up, down)
+        for h in (hist_in, hist_out):
+            assert h.is_cuda and h.dtype == torch.float32 and h.shape == (B, n_hist) and h.is_contiguous()
+        assert in_lens.is_cuda and in_lens.dtype == torch.int32 and in_lens.shape == (B,) and in_lens.is_contiguous()
+        g = gcd(up, down)
+        cap = -(-max(in_count, 0) * (up // g) // (down // g)) + n_flush
+        if out is None:
+            out = torch.empty((B, cap), dtype=torch.float32, device=cur.device)
+        out_lens = torch.empty((B,), dtype=torch.int32, device=cur.device) if return_lens else None
+        check(self.lib.tts_resample_poly_chunk(self.handle, ctypes.c_void_p(cur.data_ptr()), S, int(in_start), in_count,
+                                               ctypes.c_void_p(in_lens.data_ptr()), B, up, down,
+                                               ctypes.c_void_p(hist_in.data_ptr()), ctypes.c_void_p(hist_out.data_ptr()),
+                                               ctypes.c_void_p(out.data_ptr()), out.shape[1], out.shape[1],
+                                               ctypes.c_void_p(out_lens.data_ptr()) if return_lens else None,
+                                               _stream_ptr(stream)),
+              "tts_resample_poly_chunk")
         return out, out_lens
 
     @property

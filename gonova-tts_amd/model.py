@@ -25,7 +25,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from .config import AcousticConfig, VocoderConfig, SAMPLE_RATE
-from .engine import HipEngine
+from .engine import HipEngine, resample_chunk_counts, resample_history
 from .text import tokenize_batch
 from .weights import make_acoustic_weights, make_vocoder_weights
 
@@ -217,26 +217,41 @@ class GonovaTTS:
     # -------------------------------------------------------------- streaming
     STREAM_CONTEXT = 16  # mel frames of context per side; HiFi-GAN V1's receptive field is < 13
 
+    streams_resampled = True  # stream_tokens(output_rate=...) / stream_batch cut a resampled stream too
+
     def stream_tokens(self, tokens: np.ndarray, lens: np.ndarray, chunk_frames: int = 32,
                       context: Optional[int] = None, durations: Optional[np.ndarray] = None, stream=None,
-                      speaker_embedding: Optional[np.ndarray] = None):
+                      speaker_embedding: Optional[np.ndarray] = None, output_rate: Optional[int] = None):
         """Sub-sentence streaming: one acoustic pass, then the vocoder
         runs on windows [c0 - ctx, c0 + chunk + ctx) and keeps the middle `chunk` frames.
         With ctx >= the receptive field every kept sample is computed from the same inputs
         in the same order as the full-utterance pass, so the concatenated chunks equal it.
 
         Yields (c0, wav_chunk cuda float32 [B, chunk*256], valid samples per utterance np [B]).
-        Chunks are at the vocoder's native 22,050 Hz whatever `sr` is (a resampled stream would
-        need the resampler's own filter context across chunk edges)."""
+        output_rate None (or the vocoder's 22,050 Hz, whatever `sr` is): native chunks.  Another
+        rate: every chunk goes through the chunked resampler (tts_resample_poly_chunk), which
+        carries the filter's history between chunks; wav_chunk is then [B, cap] at that rate with
+        cap = ceil(chunk*256*up/down) + n_flush, and the valid counts differ from chunk to chunk
+        (an utterance's last chunk also brings the outputs held back until its end is known).  The
+        valid parts concatenate to synthesize_tokens' output at that rate, bit for bit."""
         import torch
         with torch.cuda.device(self.engine.device_index):  # (see synthesize_tokens)
-            yield from self._stream_tokens(tokens, lens, chunk_frames, context, durations, stream, speaker_embedding)
+            for c0, wav, valid, _ in self._stream_tokens(tokens, lens, chunk_frames, context, durations, stream,
+                                                         speaker_embedding, output_rate):
+                yield c0, wav, valid
 
-    def _stream_tokens(self, tokens, lens, chunk_frames, context, durations, stream, speaker_embedding):
+    def _stream_tokens(self, tokens, lens, chunk_frames, context, durations, stream, speaker_embedding,
+                       output_rate=None):
+        """stream_tokens' generator; yields a fourth item, ended np bool [B]: the utterance has no
+        frame past this chunk."""
         import torch
         ctx = self.STREAM_CONTEXT if context is None else context
         dev = self.engine.torch_device
         B, N = tokens.shape
+        hop = self.vocoder_cfg.hop
+        rs = None
+        if output_rate and int(output_rate) != self.native_sr:
+            rs = _ChunkResampler(self.engine, B, int(output_rate), self.native_sr, hop, chunk_frames, dev, stream)
         tok, tl, dd = _upload_i32((tokens, lens, durations), dev, stream)
         t_cap = max(64, int(self.FRAMES_PER_TOKEN_CAP * N)) if durations is None else \
             max(1, int(np.asarray(durations).sum(axis=1).max()))
@@ -259,7 +274,10 @@ class GonovaTTS:
             rd = _HostRead(dur, mel_lens, rw, stream)
             if early:
                 win_lens = torch.clamp(mel_lens, min=0, max=w1).to(torch.int32)
-                first = (w1, tc, self.engine.vocoder_chunk(mel[:, :w1].contiguous(), win_lens, 0, tc, stream=stream))
+                wav = self.engine.vocoder_chunk(mel[:, :w1].contiguous(), win_lens, 0, tc, stream=stream)
+                if rs is not None:  # its resample ahead of the read too (discarded with it: chunk 0
+                    wav = rs.run(wav, 0, mel_lens)  # starts the history anew)
+                first = (w1, tc, wav)
             need, lens_h, tripped = rd.result()  # one host read before the first chunk is handed over
             fell_back = False
             if tripped:  # range guard: the acoustic pass again on the fp32 encoder
@@ -288,7 +306,6 @@ class GonovaTTS:
             # host enqueues faster than the GPU drains either way)
             lens_h = _mel_lens_host(lens, durations, t_cap)
         T = int(lens_h.max()) if B else 0
-        hop = self.vocoder_cfg.hop
         for c0 in range(0, T, chunk_frames):
             tc = min(chunk_frames, T - c0)
             w0 = max(0, c0 - ctx)
@@ -299,6 +316,8 @@ class GonovaTTS:
                 win = mel[:, w0:w1].contiguous()
                 win_lens = torch.clamp(mel_lens - w0, min=0, max=w1 - w0).to(torch.int32)
                 wav = self.engine.vocoder_chunk(win, win_lens, c0 - w0, tc, stream=stream)
+                if rs is not None:
+                    wav = rs.run(wav, c0, mel_lens)
             if c0 == 0 and durations is not None and rw is not None:
                 # given durations made no host read so far: the range word is read here, where the
                 # consumer would wait for this chunk anyway; out of range -> fp32 encoder, chunk again
@@ -309,9 +328,14 @@ class GonovaTTS:
                     win = mel[:, w0:w1].contiguous()
                     win_lens = torch.clamp(mel_lens - w0, min=0, max=w1 - w0).to(torch.int32)
                     wav = self.engine.vocoder_chunk(win, win_lens, c0 - w0, tc, stream=stream)
+                    if rs is not None:  # (chunk 0 again: the history starts anew)
+                        wav = rs.run(wav, c0, mel_lens)
             first = None
-            valid = np.clip(lens_h - c0, 0, tc) * hop
-            yield c0, wav, valid
+            if rs is not None:
+                valid = rs.counts(lens_h, c0, tc)
+            else:
+                valid = np.clip(lens_h - c0, 0, tc) * hop
+            yield c0, wav, valid, lens_h <= c0 + tc
 
     def _voice_groups(self, n: int, speaker_embeddings):
         """Sentence index groups that share one engine pass: on a multi-speaker model the
@@ -332,31 +356,31 @@ class GonovaTTS:
         """Sub-sentence streaming of many sentences in one batched pass (the service's opt-in
         `stream_frames` mode): yields, per vocoder chunk, a list of (sentence index, float32
         samples of that chunk, sentence finished).  A sentence's pieces concatenate to the
-        stream_tokens output, which equals the full pass (stream_tokens).  With an output rate
-        other than the vocoder's the pieces would need the resampler's filter context across
-        chunk edges, so each sentence comes as one piece then."""
+        stream_tokens output, which equals the full pass (stream_tokens) -- at `sr`: with an
+        output rate other than the vocoder's the chunks come through the chunked resampler
+        (stream_tokens(output_rate=sr)) and the pieces concatenate to generate_batch's audio at
+        that rate, bit for bit; their lengths then differ from chunk to chunk."""
         if not texts:
             return
-        if self.sr != self.native_sr:
-            yield [(i, a, True) for i, a in enumerate(self.generate_batch(texts, speaker_embeddings))]
-            return
-        with self._lock:
+        import torch
+        with self._lock, torch.cuda.device(self.engine.device_index):
             for idx, spk in self._voice_groups(len(texts), speaker_embeddings):
                 tokens, lens = tokenize_batch([texts[i] for i in idx])
                 done = [False] * len(idx)
-                for c0, wav, valid in self.stream_tokens(tokens, lens, chunk_frames, speaker_embedding=spk):
+                for c0, wav, valid, ended in self._stream_tokens(tokens, lens, chunk_frames, None, None, None, spk,
+                                                                 self.sr):
                     host = _to_host(wav)
-                    full = host.shape[1]
                     out = []
                     for r, i in enumerate(idx):
                         if done[r]:
                             continue
-                        v = int(valid[r])
-                        done[r] = v < full  # a short (or empty) piece is the sentence's last
-                        out.append((i, host[r, :v].astype(np.float32, copy=False), done[r]))
+                        # (the piece's length says nothing at a resampled rate: the sentence is
+                        # finished with the chunk that holds its last frame)
+                        done[r] = bool(ended[r])
+                        out.append((i, host[r, :int(valid[r])].astype(np.float32, copy=False), done[r]))
                     yield out
                 last = [(i, np.zeros(0, np.float32), True) for r, i in enumerate(idx) if not done[r]]
-                if last:  # sentences whose length is a whole number of chunks
+                if last:  # sentences without a frame
                     yield last
 
     def generate_batch(self, texts: List[str], speaker_embeddings: Optional[List[Optional[np.ndarray]]] = None,
@@ -442,6 +466,34 @@ class PendingRange:
         with torch.cuda.device(m.engine.device_index), m._range_fallback():
             wav, wav_lens, _ = m._synthesize_once(*self.args)
         return wav, np.asarray(wav_lens, np.int64)
+
+
+class _ChunkResampler:
+    """The output-rate stage of one stream_tokens generator: the reduced ratio and the two history
+    buffers tts_resample_poly_chunk alternates between (chunk k reads hist[k % 2] and writes the
+    other; chunk 0 reads none, so running it again -- an early first chunk recomputed, a range-guard
+    rerun -- starts the history anew)."""
+
+    def __init__(self, engine, B, rate, native, hop, chunk_frames, dev, stream):
+        import torch
+        g = gcd(rate, native)
+        self.engine, self.up, self.down = engine, rate // g, native // g
+        self.hop, self.chunk_frames, self.stream = hop, chunk_frames, stream
+        self.hist = torch.empty((2, B, resample_history(self.up, self.down)[0]), dtype=torch.float32, device=dev)
+        self._lens_of = self._in_lens = None
+
+    def run(self, wav, c0, mel_lens):
+        """The chunk of frames starting at c0 (wav [B, frames*hop]) -> its samples at the output rate."""
+        if self._lens_of is not mel_lens:  # the utterances' final sample counts, already on the device
+            self._lens_of, self._in_lens = mel_lens, (mel_lens * self.hop).int()
+        k = (c0 // self.chunk_frames) & 1
+        out, _ = self.engine.resample_chunk(wav, c0 * self.hop, self._in_lens, self.up, self.down, self.hist[k],
+                                            self.hist[1 - k], return_lens=False, stream=self.stream)
+        return out
+
+    def counts(self, lens_h, c0, tc):
+        """Valid output samples per utterance of that chunk (host arithmetic, no device read)."""
+        return resample_chunk_counts(lens_h * self.hop, c0 * self.hop, tc * self.hop, self.up, self.down)
 
 
 _UPLOAD_STREAMS: Dict[int, object] = {}

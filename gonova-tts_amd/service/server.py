@@ -11,7 +11,8 @@
   an error and the list is empty;
 * opt-in sub-sentence streaming: a `"stream_frames": N` field (or the
   service's `stream_frames` default) splits each sentence's audio into frames of N mel frames
-  (N x 256 samples, the last one shorter) as the vocoder produces them, in sentence order, with
+  (N x 256 samples, the last one shorter; at a resampled rate, e.g. 24 kHz, what the chunked
+  resampler emits per chunk) as the vocoder produces them, in sentence order, with
   the same final marker (its chunk_id = frames sent).  The reference accepts `streaming` /
   `chunk_size` and ignores them (`core/synthesizer.py:226,245,320-321`); so does this service,
   and without `stream_frames` the framing stays one frame per sentence;
@@ -114,8 +115,9 @@ class TTSService:
             for text in WARMUP_TEXTS:  # the reference's three warmups (synthesizer.py:197-207)
                 await loop.run_in_executor(None, m.generate_batch, [text])
         if self.stream_frames and not self.can_stream():
-            raise ValueError("stream_frames needs the vocoder's native sample rate: this model resamples "
-                             f"to {getattr(self.model, 'sr', None)} Hz, which needs filter context across frames")
+            raise ValueError("stream_frames needs the vocoder's native sample rate or a model that declares "
+                             f"streams_resampled: this model resamples to {getattr(self.model, 'sr', None)} Hz "
+                             "per sentence only")
         sr = getattr(self.model, "sr", 22050)
         self.queues = TTSQueueManager(sample_rate=sr)
         await self.queues.start()
@@ -130,11 +132,15 @@ class TTSService:
         self.is_loaded = True
 
     def can_stream(self) -> bool:
-        """Sub-sentence frames come straight from the vocoder's chunks, at its native rate; a
-        model that resamples (e.g. to the 24 kHz the reference's clients assume) cannot cut its
-        output at chunk edges without the resampler's filter context (model.stream_batch)."""
+        """Sub-sentence frames come from the vocoder's chunks: at its native rate, or, from a model
+        that declares `streams_resampled` (GonovaTTS: its stream_batch carries the resampler's
+        history across chunk edges), at the rate it resamples to (e.g. the 24 kHz the reference's
+        clients assume).  A resampling model without the attribute cuts per sentence only."""
         m = self.model
-        return getattr(m, "stream_batch", None) is not None and getattr(m, "sr", 0) == getattr(m, "native_sr", getattr(m, "sr", 0))
+        if getattr(m, "stream_batch", None) is None:
+            return False
+        sr = getattr(m, "sr", 0)
+        return sr == getattr(m, "native_sr", sr) or bool(getattr(m, "streams_resampled", False))
 
     def _stream_frames(self, v) -> int:
         """A request's (or the service default's) `stream_frames`: 0 = one frame per sentence;
@@ -232,7 +238,8 @@ class TTSService:
                 frames = self._stream_frames(data.get("stream_frames", self.stream_frames))
                 if frames and not self.can_stream():
                     raise ValueError("stream_frames is not available: this model resamples to "
-                                     f"{getattr(self.model, 'sr', None)} Hz; omit it for one frame per sentence")
+                                     f"{getattr(self.model, 'sr', None)} Hz per sentence only (no "
+                                     "streams_resampled); omit it for one frame per sentence")
             except ValueError as e:
                 # a request refused before it is queued: the client is told (reference error shape,
                 # server.py:244-247), instead of waiting for a marker that never comes

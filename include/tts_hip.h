@@ -63,7 +63,8 @@ typedef struct tts_engine tts_engine;
  *      the call returns)
  *   4  range guard of the exact encoder: tts_acoustic_range_flag / tts_acoustic_set_precision,
  *      TTS_ENCODER_F32
- *   5  tts_device_bytes (the library's device memory per HIP device); additive */
+ *   5  tts_device_bytes (the library's device memory per HIP device); additive.  Also under 5,
+ *      additive: tts_resample_poly_chunk / tts_resample_history (a caller detects them by symbol) */
 #define TTS_ABI_VERSION 5
 int tts_abi_version(void);
 
@@ -218,6 +219,32 @@ int tts_resample_poly(tts_engine* eng, const float* d_in, int64_t in_stride, con
 /* Host only: the padded filter taps tts_resample_poly uses (float64, scaled by up); returns the
  * tap count (h filled only when cap >= it), *n_pre_remove = leading outputs scipy discards. */
 int tts_resample_filter(int up, int down, double* h, int cap, int* n_pre_remove);
+
+/* The same resampling of a stream that arrives in chunks (sub-sentence streaming at 24 kHz): the
+ * outputs of all chunks, one after another, are tts_resample_poly's of the whole input, bit for
+ * bit.  Per call, for each utterance b:
+ *   d_in       [B][in_stride]: its samples [in_start, in_start + in_count) (the same for every b)
+ *   d_in_lens  [b] = n_in, its FINAL total length (known before the first chunk: mel_lens * 256);
+ *              samples of d_in at or past n_in are never read into a sum
+ *   d_hist_in  [B][n_hist]: the n_hist samples before in_start (not read, may be NULL, when
+ *              in_start == 0)
+ *   d_hist_out [B][n_hist]: the n_hist samples before in_start + in_count, for the next call
+ *              (a buffer other than d_hist_in; in_count < n_hist is fine)
+ *   d_out      [B][out_stride]: outputs [emitted(in_start), emitted(in_start + in_count)), then zeros
+ *              up to out_cap; d_out_lens[b] (NULL: not written) their count, where
+ *              emitted(E) = n_out = ceil(n_in*up/down) if E >= n_in, else
+ *                           min(n_out, max(0, ceil(E*up/down) - n_flush))
+ *              -- an output is emitted once its newest tap is inside the samples seen, and the
+ *              last <= n_flush outputs of an utterance with the chunk it ends in.
+ * out_cap must be >= ceil(in_count*up/down) + n_flush (no chunk emits more); n_hist and n_flush
+ * come from tts_resample_history (20 and 11 at 160/147).  One kernel launch, no host sync. */
+int tts_resample_poly_chunk(tts_engine* eng, const float* d_in, int64_t in_stride, int64_t in_start, int in_count,
+                            const int32_t* d_in_lens, int B, int up, int down, const float* d_hist_in,
+                            float* d_hist_out, float* d_out, int64_t out_stride, int out_cap, int32_t* d_out_lens,
+                            void* stream);
+/* Host only: *n_hist = history samples tts_resample_poly_chunk carries between chunks (taps per
+ * output - 1), *n_flush = scipy's n_pre_remove (outputs held back until the utterance ends). */
+int tts_resample_history(int up, int down, int* n_hist, int* n_flush);
 
 /* Thread-local message describing the last failure on this thread. */
 const char* tts_last_error(void);
