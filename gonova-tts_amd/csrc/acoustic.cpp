@@ -153,7 +153,9 @@ struct AcousticModel::Impl {
     run(L, x, x_rows, lens, y, y_rows, B, d, s, prof, 1.f, ACT_NONE, alpha, r1, &ln);
   }
   Profiler* prof = nullptr;
-  int D = 384, H = 2, V = 78, NMEL = 80, FFN = 1536, PRED = 256;
+  // FFN / PRED / PNW: the widest FFN of either stack, the widest conv output of any predictor
+  // layer, the widest postnet layer (check_envelope; the workspace is sized from them)
+  int D = 384, H = 2, V = 78, NMEL = 80, FFN = 1536, PRED = 256, PNW = 256;
   float eps = 1e-5f;
   void* embed = nullptr;
   std::vector<ConformerLayer> enc, dec;
@@ -205,6 +207,185 @@ struct AcousticModel::Impl {
     const std::vector<float>* p = get(n);
     if (!p) throw TtsError(TTS_ERR_STATE, "missing acoustic weight: " + n);
     return *p;
+  }
+
+  // The supported acoustic envelope, checked from the weight shapes before
+  // anything is uploaded or launched: a model passes only if every dtype, encoder precision and
+  // kernel-path switch can run it, so nothing that loads fails (or writes past a buffer) at its
+  // first forward.  Each message names the tensor and the limit.  Sets D, H, V, NMEL and the
+  // widths the workspace is sized from (FFN, PRED, PNW).
+  // FFN widths above 2048 and postnet layers above 512 channels are refused only because none has
+  // been run (tests/test_acoustic_configs_gpu.py goes to 1536 / 512).
+  // The conv taps (k - 1 <= CONV_HALO_MAX) and the depthwise kernel (GLU_DWCONV_MAX_K) are held to
+  // what the launchers take, though the tests run no FFN above 5 taps, no predictor or postnet
+  // conv above 5 and no depthwise kernel above 31.
+  static constexpr int FFN_MAX = 2048, POSTNET_MAX = 512, MEL_BINS = 80;
+  void check_envelope(const GetData& get, const GetShape& shape) {
+    auto bad = [](const std::string& what) { throw TtsError(TTS_ERR_INVALID, "acoustic envelope: " + what); };
+    auto str = [](int64_t v) { return std::to_string(v); };
+    auto dims = [&](const std::string& n, size_t rank) {
+      const auto s = shape(n);
+      if (!get(n)) bad(n + ": missing");
+      if (s.size() != rank) bad(n + ": expected a " + std::to_string(rank) + "-D tensor");
+      return s;
+    };
+    auto vec = [&](const std::string& n, int64_t c) {  // a per-channel vector (any rank) of c values
+      if (!get(n) || (int64_t)get(n)->size() != c) bad(n + ": expected " + std::to_string(c) + " values");
+    };
+    auto vec_opt = [&](const std::string& n, int64_t c) {  // a conv's bias: may be absent
+      if (get(n)) vec(n, c);
+    };
+    // a conv [Cout][Cin][k] on the implicit-GEMM kernels (conv_gemm_check in every dtype: 16-byte
+    // input rows are 8 16-bit channels), padded (k - 1) / 2 on both sides
+    auto conv3 = [&](const std::string& n, int64_t cin) {
+      const auto s = dims(n, 3);
+      if (s[1] != cin) bad(n + ": " + str(s[1]) + " input channels after a layer of " + str(cin));
+      if (s[1] <= 0 || s[1] % 8)
+        bad(n + ": input channel count " + str(s[1]) + " is not a multiple of 8 (rows of 16-byte pieces)");
+      if (s[0] <= 0 || s[0] % 4) bad(n + ": output channel count " + str(s[0]) + " is not a multiple of 4");
+      if (s[2] < 1 || s[2] % 2 == 0) bad(n + ": kernel size " + str(s[2]) + " is not odd (padding (k - 1) / 2)");
+      if (s[2] - 1 > CONV_HALO_MAX)
+        bad(n + ": receptive field k - 1 = " + str(s[2] - 1) + " exceeds " + str(CONV_HALO_MAX) + " rows");
+      return s;
+    };
+    auto mat = [&](const std::string& n, int64_t co, int64_t ci) {
+      const auto s = shape(n);
+      if (!get(n) || s.size() < 2 || s[0] != co || s[1] != ci || (int64_t)get(n)->size() != co * ci)
+        bad(n + ": expected [" + str(co) + "][" + str(ci) + "]");
+    };
+    const auto es = dims("encoder.embed.weight", 2);
+    V = (int)es[0];
+    D = (int)es[1];
+    if (V < 1) bad("encoder.embed.weight: empty vocabulary");
+    if (D <= 0 || D % 64 || D > LN_MAX_C)
+      bad("encoder.embed.weight: hidden size " + str(D) + " is not a multiple of 64 of at most " + str(LN_MAX_C) +
+          " (64-channel tiles; one LayerNorm row per wave)");
+    const std::string u0 = "encoder.conformer_layers.0.self_attn.pos_bias_u";
+    const auto us = dims(u0, 2);
+    H = (int)us[0];
+    if (H < 1 || us[0] * us[1] != D) bad(u0 + ": [" + str(us[0]) + "][" + str(us[1]) + "] does not split the hidden size " + str(D));
+    if (us[1] % 16) bad(u0 + ": head size " + str(us[1]) + " is not a multiple of 16");
+    FFN = 0;
+    for (const char* st : {"encoder.", "decoder."}) {
+      int n = 0;
+      for (;; ++n) {
+        const std::string p = std::string(st) + "conformer_layers." + std::to_string(n) + ".";
+        const std::string a = p + "self_attn.";
+        if (!get(a + "pos_bias_u")) break;
+        // every layer of both stacks has the encoder's hidden size and heads (one workspace, one
+        // relative-position table width)
+        for (const char* pb : {"pos_bias_u", "pos_bias_v"}) {
+          const auto s = dims(a + pb, 2);
+          if (s[0] != H || s[1] != D / H)
+            bad(a + pb + ": [" + str(s[0]) + "][" + str(s[1]) + "] where " + u0 + " is [" + str(H) + "][" + str(D / H) + "]");
+        }
+        for (const char* l : {"linear_q", "linear_k", "linear_v", "linear_out"}) {
+          mat(a + l + ".weight", D, D);
+          vec(a + l + ".bias", D);
+        }
+        mat(a + "linear_pos.weight", D, D);
+        // the FFN width may differ between layers and stacks (H1 is sized for the widest); the two
+        // FFNs of a layer share one kernel size
+        const int64_t kf = conv3(p + "feed_forward.conv1.weight", D)[2];
+        for (const char* ff : {"feed_forward.", "feed_forward_macaron."}) {
+          const auto c1 = conv3(p + ff + "conv1.weight", D);
+          const auto c2 = conv3(p + ff + "conv2.weight", c1[0]);
+          if (c2[0] != D) bad(p + ff + "conv2.weight: " + str(c2[0]) + " output channels for the hidden size " + str(D));
+          if (c1[2] != kf || c2[2] != kf)
+            bad(p + ff + (c1[2] != kf ? "conv1" : "conv2") + ".weight: kernel size " + str(c1[2] != kf ? c1[2] : c2[2]) +
+                " where " + p + "feed_forward.conv1.weight has " + str(kf) + " (the FFN convs of a layer share one)");
+          if (c1[0] > FFN_MAX)
+            bad(p + ff + "conv1.weight: FFN width " + str(c1[0]) + " exceeds " + str(FFN_MAX) + " (none wider has been run)");
+          vec_opt(p + ff + "conv1.bias", c1[0]);
+          vec_opt(p + ff + "conv2.bias", D);
+          FFN = std::max(FFN, (int)c1[0]);
+        }
+        const std::string c = p + "conv_module.";
+        const auto p1 = conv3(c + "pointwise_conv1.weight", D);
+        const auto p2 = conv3(c + "pointwise_conv2.weight", D);
+        if (p1[0] != 2 * D || p1[2] != 1) bad(c + "pointwise_conv1.weight: expected [" + str(2 * D) + "][" + str(D) + "][1]");
+        if (p2[0] != D || p2[2] != 1) bad(c + "pointwise_conv2.weight: expected [" + str(D) + "][" + str(D) + "][1]");
+        vec_opt(c + "pointwise_conv1.bias", 2 * D);
+        vec_opt(c + "pointwise_conv2.bias", D);
+        const auto dw = dims(c + "depthwise_conv.weight", 3);
+        if (dw[0] != D || dw[1] != 1) bad(c + "depthwise_conv.weight: expected [" + str(D) + "][1][k]");
+        if (dw[2] < 1 || dw[2] % 2 == 0) bad(c + "depthwise_conv.weight: kernel size " + str(dw[2]) + " is not odd");
+        if (dw[2] > GLU_DWCONV_MAX_K)
+          bad(c + "depthwise_conv.weight: kernel size " + str(dw[2]) + " exceeds " + str(GLU_DWCONV_MAX_K) +
+              " (the depthwise kernel's LDS tile)");
+        for (const char* v : {"depthwise_conv.bias", "norm.weight", "norm.bias", "norm.running_mean", "norm.running_var"})
+          vec(c + v, D);
+        for (const char* l : {"ff_macaron_layer_norm", "self_attn_layer_norm", "conv_layer_norm", "ff_layer_norm",
+                              "final_layer_norm"}) {
+          vec(p + l + ".weight", D);
+          vec(p + l + ".bias", D);
+        }
+      }
+      if (n == 0) bad(std::string(st) + "conformer_layers.0.self_attn.pos_bias_u: the stack has no layer");
+    }
+    // variance predictors: conv -> ReLU -> LayerNorm per layer, LayerNorm + Linear(C -> 1) at the end
+    PRED = 0;
+    for (const char* pr : {"pitch_predictor.", "energy_predictor.", "duration_predictor."}) {
+      int64_t cin = D;
+      int n = 0;
+      for (;; ++n) {
+        const std::string q = std::string(pr) + "conv_layers." + std::to_string(n) + ".";
+        if (!get(q + "conv.weight")) break;
+        const auto s = conv3(q + "conv.weight", cin);
+        if (s[0] > LN_PRED_MAX_C)
+          bad(q + "conv.weight: " + str(s[0]) + " output channels exceed " + str(LN_PRED_MAX_C) +
+              " (the predictors' LayerNorm kernels)");
+        vec_opt(q + "conv.bias", s[0]);
+        vec(q + "layer_norm.weight", s[0]);
+        vec(q + "layer_norm.bias", s[0]);
+        PRED = std::max(PRED, (int)s[0]);
+        cin = s[0];
+      }
+      if (n == 0) bad(std::string(pr) + "conv_layers.0.conv.weight: a predictor needs at least one layer");
+      vec(std::string(pr) + "linear.weight", cin);
+      vec(std::string(pr) + "linear.bias", 1);
+    }
+    // the pitch / energy embeddings are applied per token: Conv1d(1 -> D) of one tap
+    for (const char* e : {"pitch_embed.conv.", "energy_embed.conv."}) {
+      const auto s = dims(std::string(e) + "weight", 3);
+      if (s[0] != D || s[1] != 1 || s[2] != 1)
+        bad(std::string(e) + "weight: [" + str(s[0]) + "][" + str(s[1]) + "][" + str(s[2]) + "]; expected [" + str(D) +
+            "][1][1] (a kernel size of 1)");
+      vec(std::string(e) + "bias", D);
+    }
+    if (get("projection.weight")) {
+      const auto ps = dims("projection.weight", 2);  // [D][D + E]
+      if (ps[0] != D || ps[1] <= D) bad("projection.weight: expected [" + str(D) + "][" + str(D) + " + E]");
+      vec("projection.bias", D);
+    }
+    // postnet: feat_out (hidden -> mel bins), then convs with BatchNorm folded; the last returns to
+    // the mel bins (its output is added to feat_out's)
+    const std::string fo = "speech_decoder_postnet.feat_out.weight";
+    const auto fs = dims(fo, 2);
+    NMEL = (int)fs[0];
+    if (fs[1] != D) bad(fo + ": " + str(fs[1]) + " input channels for the hidden size " + str(D));
+    // every forward writes its mel as [B][Tcap][80] floats into the caller's buffer (tts_hip.h)
+    if (NMEL != MEL_BINS)
+      bad(fo + ": " + str(NMEL) + " mel bins; the forwards write a fixed [B][T][" + str(MEL_BINS) + "] output");
+    vec_opt("speech_decoder_postnet.feat_out.bias", NMEL);
+    PNW = 0;
+    int64_t cin = NMEL;
+    int n = 0;
+    for (;; ++n) {
+      const std::string p = "speech_decoder_postnet.layers." + std::to_string(n) + ".";
+      if (!get(p + "conv.weight")) break;
+      const auto s = conv3(p + "conv.weight", cin);
+      if (s[0] > POSTNET_MAX)
+        bad(p + "conv.weight: " + str(s[0]) + " output channels exceed " + str(POSTNET_MAX) + " (none wider has been run)");
+      for (const char* v : {"batch_norm.weight", "batch_norm.bias", "batch_norm.running_mean", "batch_norm.running_var"})
+        vec(p + v, s[0]);
+      PNW = std::max(PNW, (int)s[0]);
+      cin = s[0];
+    }
+    if (n == 0) bad("speech_decoder_postnet.layers.0.conv.weight: the postnet needs at least one layer");
+    if (cin != NMEL)
+      bad("speech_decoder_postnet.layers." + std::to_string(n - 1) + ".conv.weight: " + str(cin) +
+          " output channels where feat_out has " + str(NMEL) + " mel bins");
   }
 
   ConvLayer conv(const GetData& get, const GetShape& shape, const std::string& w, const std::string& b, int pad,
@@ -297,7 +478,6 @@ struct AcousticModel::Impl {
       P.convs.push_back(conv(get, shape, q + "conv.weight", q + "conv.bias", (k - 1) / 2));
       P.lns.push_back(ln(get, q + "layer_norm"));
     }
-    if (P.convs.empty()) throw TtsError(TTS_ERR_STATE, "predictor without layers: " + p);
     P.lin_w = upf(need(get, p + "linear.weight"));
     P.lin_b = need(get, p + "linear.bias").at(0);
     return P;
@@ -460,15 +640,19 @@ struct AcousticModel::Impl {
     auto both = [&](size_t C) { return alloc_ws(std::max(nrows * C * ee, rows * C * ed), 1); };
     X = both(D); Y = both(D); O = both(D); G = both(D);
     Qu = both(D); Qv = both(D);
+    // H1: the FFN hidden rows of every layer of both stacks (FFN = the widest); QKV: the fused
+    // projection's 3 D; A: the first pointwise conv's 2 D (GLU input)
     H1 = both(FFN); QKV = both(3 * D); A = both(2 * D);
     Vt = alloc_ws(std::max((size_t)B * H * dk * rup(N, 16) * ee, (size_t)B * H * dk * rup(Tm, 16) * ed), 1);
     ENC = alloc_ws(nrows * D, ee);
     SPK = alloc_ws((size_t)B * D, ee);
-    PB1 = alloc_ws(nrows * PRED, std::max<size_t>(ee, 2)); PB2 = alloc_ws(nrows * PRED, ee);  // PB1 also holds f32 logd [B][N]
-    VP = alloc_ws(nrows * 3 * 256, 4);  // the batched first predictor convs (fp32, <= 256 channels each)
+    // every predictor's hidden rows alternate between PB1 and PB2 (PRED = the widest conv output of
+    // any predictor layer, pitch and energy included); PB1 also holds f32 logd [B][N]
+    PB1 = alloc_ws(nrows * PRED, std::max<size_t>(ee, 2)); PB2 = alloc_ws(nrows * PRED, ee);
+    VP = alloc_ws(nrows * 3 * LN_PRED_MAX_C, 4);  // the batched first predictor convs (fp32, <= 256 channels each)
     const size_t trows = (size_t)B * rup(T + dec_pad(), 32);
     BEF = alloc_ws(trows * NMEL, ed); MELT = alloc_ws(trows * NMEL, ed);
-    PN1 = alloc_ws(trows * PRED, ed); PN2 = alloc_ws(trows * PRED, ed);
+    PN1 = alloc_ws(trows * PNW, ed); PN2 = alloc_ws(trows * PNW, ed);  // the postnet's hidden rows (PNW = its widest layer)
     f_pitch = (float*)alloc_ws(nrows, 4); f_energy = (float*)alloc_ws(nrows, 4); f_logd = (float*)alloc_ws(nrows, 4);
     i_dur = (int*)alloc_ws((size_t)B * N, 4);
     i_tokmap = (int*)alloc_ws((size_t)B * T, 4);
@@ -780,14 +964,7 @@ void AcousticModel::finalize(const GetData& get, const GetShape& shape, int dtyp
   m->f32_dec_packed = m->f32_split_dec && sw(SW_F32_DEC_PACKED) != 0;
   m->enc_side = true;
   m->prof = prof;
-  const auto es = shape("encoder.embed.weight");
-  m->V = (int)es.at(0);
-  m->D = (int)es.at(1);
-  m->H = (int)shape("encoder.conformer_layers.0.self_attn.pos_bias_u").at(0);
-  m->FFN = (int)shape("encoder.conformer_layers.0.feed_forward.conv1.weight").at(0);
-  m->PRED = (int)shape("duration_predictor.conv_layers.0.conv.weight").at(0);
-  m->NMEL = (int)shape("speech_decoder_postnet.feat_out.weight").at(0);
-  if (m->D % 64 || m->D > 512 || (m->D / m->H) % 16) throw TtsError(TTS_ERR_INVALID, "unsupported hidden size");
+  m->check_envelope(get, shape);  // D, H, V, NMEL, FFN, PRED, PNW from the shapes, or a refusal
   // encoder side (bdt = dte): embedding, encoder layers, speaker projection, variance predictors
   m->embed = m->track(upload(*get("encoder.embed.weight"), m->dte));
   for (int i = 0; get("encoder.conformer_layers." + std::to_string(i) + ".self_attn.pos_bias_u"); ++i)
@@ -799,7 +976,6 @@ void AcousticModel::finalize(const GetData& get, const GetShape& shape, int dtyp
   if (get("projection.weight")) {
     const auto ps = shape("projection.weight");  // [D][D + E]
     const int din = (int)ps.at(1);
-    if ((int)ps.at(0) != m->D || din <= m->D) throw TtsError(TTS_ERR_INVALID, "bad projection.weight shape");
     m->E = din - m->D;
     const auto& pw = m->need(get, "projection.weight");
     std::vector<float> wh((size_t)m->D * m->D), we((size_t)m->D * m->E);

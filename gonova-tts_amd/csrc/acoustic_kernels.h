@@ -22,6 +22,15 @@ hipError_t launch_transpose_v(int dt, const void* qkv, const int* lens, int B, i
                               hipStream_t s);
 hipError_t launch_rel_softmax(int dt, const void* ac, const void* bd, const int* lens, int B, int H, int Tm, int Sac,
                               int Sbd, int Sk, float scale, void* p, hipStream_t s);
+// widest rows the row-wise LayerNorm kernels take: launch_layernorm / the fused post-LN tails, and
+// launch_ln_linear1 / launch_layernorm_groups (the variance predictors)
+constexpr int LN_MAX_C = 512;
+constexpr int LN_PRED_MAX_C = 256;
+// the depthwise kernels stage (128 + k - 1) rows x 64 channels of fp32 GLU output in LDS; the
+// largest odd k whose tile stays within 64 KiB (what a launch gets without asking for more)
+constexpr int GLU_DWCONV_LDS_MAX = 64 * 1024;
+constexpr int GLU_DWCONV_MAX_K = GLU_DWCONV_LDS_MAX / (64 * 4) - 128 + 1;  // 129
+// k: odd, at most GLU_DWCONV_MAX_K (else hipErrorInvalidValue)
 hipError_t launch_glu_dwconv(int dt, const void* a, const int* lens, int B, int Tm, int D, const float* w, int k,
                              const float* bias, void* out, hipStream_t s);
 hipError_t launch_ln_linear1(int dt, const void* in, int rows, int C, const float* g, const float* b, float eps,

@@ -562,7 +562,7 @@ static void launch_ln8(const T* in, T* out, int rows, int C, const float* g1, co
 
 hipError_t launch_layernorm(int dt, const void* in, void* out, int rows, int C, const float* g1, const float* b1,
                             const float* g2, const float* b2, float eps, hipStream_t s, const int* lens, int stride) {
-  if (C > 512 || (lens && stride <= 0)) return hipErrorInvalidValue;
+  if (C > LN_MAX_C || (lens && stride <= 0)) return hipErrorInvalidValue;
   dim3 grid((rows + 3) / 4);
   if (dt != DT_F32 && C % 8 == 0) {
     if (dt == DT_F16)
@@ -581,7 +581,7 @@ hipError_t launch_layernorm(int dt, const void* in, void* out, int rows, int C, 
 
 hipError_t launch_layernorm_groups(int dt, void* x, int rows, int C, int ld, const LnGroups& gp, int groups, float eps,
                                    hipStream_t s, const int* lens, int stride) {
-  if (C > 256 || groups < 1 || groups > LnGroups::MAXG || ld < groups * C || (lens && stride <= 0))
+  if (C > LN_PRED_MAX_C || groups < 1 || groups > LnGroups::MAXG || ld < groups * C || (lens && stride <= 0))
     return hipErrorInvalidValue;
   dim3 grid((rows + 3) / 4, groups);
   TTS_DISPATCH(dt, hipLaunchKernelGGL((layernorm_groups_kernel<TT, 4>), grid, dim3(256), 0, s, (TT*)x, rows, C, ld, gp,
@@ -620,6 +620,7 @@ hipError_t launch_rel_softmax(int dt, const void* ac, const void* bd, const int*
 
 hipError_t launch_glu_dwconv(int dt, const void* a, const int* lens, int B, int Tm, int D, const float* w, int k,
                              const float* bias, void* out, hipStream_t s) {
+  if (k < 1 || k % 2 == 0 || k > GLU_DWCONV_MAX_K) return hipErrorInvalidValue;  // pad = (k - 1) / 2; LDS tile
   dim3 grid((Tm + 127) / 128, (D + 63) / 64, B);
   const int epp = dt == DT_F32 ? 4 : 8;
   if ((k == 7 || k == 31) && D % epp == 0) {
@@ -638,7 +639,7 @@ hipError_t launch_glu_dwconv(int dt, const void* a, const int* lens, int B, int 
 
 hipError_t launch_ln_linear1(int dt, const void* in, int rows, int C, const float* g, const float* b, float eps,
                              const float* w, float wb, float* out, hipStream_t s) {
-  if (C > 256) return hipErrorInvalidValue;
+  if (C > LN_PRED_MAX_C) return hipErrorInvalidValue;
   TTS_DISPATCH(dt, hipLaunchKernelGGL((ln_linear1_kernel<TT, 4>), dim3((rows + 3) / 4), dim3(256), 0, s,
                                       (const TT*)in, rows, C, g, b, eps, w, wb, out));
 }

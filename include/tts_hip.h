@@ -129,7 +129,11 @@ int tts_engine_set_weight(tts_engine* eng, const char* name, const float* host_d
 /* Fold / pack / upload every weight set so far; must precede any forward.  A vocoder
  * configuration outside the supported envelope (last stage of 32 channels,
  * channel counts in multiples of 8, k % stride == 0 with an even k - stride, (k - 1) * dilation
- * <= 64) is refused here with TTS_ERR_INVALID and a tts_last_error() text naming the tensor. */
+ * <= 64) is refused here with TTS_ERR_INVALID and a tts_last_error() text naming the tensor.
+ * So is an acoustic model outside its envelope (hidden size a multiple of 64 up
+ * to 512, head size a multiple of 16, both stacks alike, conv channels in multiples of 8 in / 4
+ * out with odd k <= 65, depthwise k odd <= 129, predictors of 1+ layers of <= 256 channels,
+ * postnet of 1+ layers of <= 512, 80 mel bins), with a text beginning "acoustic envelope:". */
 int tts_engine_finalize(tts_engine* eng);
 /* Pre-size the workspace (so later calls allocate nothing and can be graph-captured). */
 int tts_engine_reserve(tts_engine* eng, int max_batch, int max_frames, int max_tokens);

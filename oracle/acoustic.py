@@ -52,9 +52,13 @@ def rel_pos_table(length, d_model, dtype=np.float32):
     """FastSpeech2ConformerRelPositionalEncoding (HF:723-767): rows for relative
     positions L-1, L-2, ..., 0, ..., -(L-1); returns [2L-1, d_model].
 
-    The angle p*div is rounded to float32 first, as torch computes it.
+    The frequencies and the angle p*div are rounded to float32 first, as torch computes them.
+    The frequency is the correctly rounded float32 exp of its float32 argument (what glibc's expf
+    returns): numpy's vectorised float32 exp is one ulp off on about half of these arguments and
+    torch's on a few, and one ulp of a frequency moves a mel value by up to 1e-6.
     """
-    div = np.exp(np.arange(0, d_model, 2, dtype=np.float32) * np.float32(-(math.log(10000.0) / d_model)))
+    arg = np.arange(0, d_model, 2, dtype=np.float32) * np.float32(-(math.log(10000.0) / d_model))
+    div = np.exp(arg.astype(np.float64)).astype(np.float32)
     pos = np.arange(length - 1, -length, -1, dtype=np.float32)[:, None]  # L-1 .. -(L-1)
     ang = (pos * div[None, :]).astype(np.float32).astype(np.float64)
     pe = np.zeros((2 * length - 1, d_model), np.float64)
@@ -87,8 +91,9 @@ def rel_mha(x, pos_emb, w, p, num_heads):
     i = np.arange(L)[:, None]
     j = np.arange(L)[None, :]
     bd = bd_full[:, i, (L - 1) - i + j]
-    scores = (ac + bd) / np.float32(math.sqrt(dk))
-    attn = softmax(scores.astype(np.float32), -1)
+    # (the scale and the softmax in the working dtype: a float64 run keeps float64 throughout)
+    scores = (ac + bd) / x.dtype.type(math.sqrt(dk))
+    attn = softmax(scores, -1)
     o = (attn @ v.transpose(1, 0, 2)).transpose(1, 0, 2).reshape(L, D)
     return o @ w[p + "linear_out.weight"].T + w[p + "linear_out.bias"]
 
@@ -129,7 +134,7 @@ def conformer_layer(x, pos_emb, w, p, num_heads):
 def conformer_stack(x, w, prefix, n_layers, num_heads):
     """FastSpeech2ConformerEncoder.forward (HF:803-867) after the input embedding."""
     L, D = x.shape
-    x = x * np.float32(math.sqrt(D))  # RelPositionalEncoding input_scale (HF:763)
+    x = x * x.dtype.type(math.sqrt(D))  # RelPositionalEncoding input_scale (HF:763)
     pos_emb = rel_pos_table(L, D, x.dtype)
     for i in range(n_layers):
         x = conformer_layer(x, pos_emb, w, f"{prefix}conformer_layers.{i}.", num_heads)
