@@ -83,6 +83,30 @@ class VocoderConfig:
         return asdict(self)
 
 
+def vocoder_context_frames(cfg: VocoderConfig = VocoderConfig()) -> Tuple[int, int]:
+    """Mel frames of context (left, right) a streaming window needs around a chunk so that the
+    chunk's samples are computed from exactly the inputs the whole-utterance pass reads: the
+    generator's receptive field, counted in frames.
+
+    Exact integer interval arithmetic, backwards from the last stage's rows [0, hop - 1] of one
+    frame: conv_post and conv_pre reach 3 rows per side (7 taps); a stage's MRF reaches the largest,
+    over its resblocks, of sum over pairs (k-1)/2 * (d+1) (the dilated conv plus the plain one);
+    a transposed conv (k, s, p = (k-s)/2) maps output rows [a, b] to the input rows
+    [ceil((a + p - (k-1)) / s), floor((b + p) / s)] (out[to] sums x[ti] w[j] over to = ti*s - p + j).
+    The answer is how far the frame interval reaches below 0 and above 0.  The engine derives the
+    same pair from its loaded layers (tts_vocoder_context); V1 gives (13, 13)."""
+    a, b = -3, cfg.hop - 1 + 3  # conv_post
+    for i in reversed(range(len(cfg.upsample_rates))):
+        reach = max(sum((k - 1) // 2 * (d + 1) for d in dils)
+                    for k, dils in zip(cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes))
+        a, b = a - reach, b + reach
+        k, s = cfg.upsample_kernel_sizes[i], cfg.upsample_rates[i]
+        p = (k - s) // 2
+        a, b = -((-(a + p - (k - 1))) // s), (b + p) // s  # ceil, floor
+    a, b = a - 3, b + 3  # conv_pre
+    return -a, b
+
+
 def vocoder_flops_per_sample(cfg: VocoderConfig = VocoderConfig()) -> float:
     """Algorithmic multiply-add FLOPs (2/MAC) per output sample of the vocoder.
 

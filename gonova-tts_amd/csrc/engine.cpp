@@ -381,6 +381,39 @@ struct tts_engine {
     v.loaded = true;
   }
 
+  // The generator's receptive field in mel frames (tts_vocoder_context), from the packed layers:
+  // the last stage's rows [0, hop - 1] of one frame, taken back through every layer in exact
+  // integer interval arithmetic.  A conv of `taps` taps, dilation d and left padding `pad` reads
+  // rows [a - pad, b + (taps-1)*d - pad]; a transposed conv (k = taps*s, stride s, padding p)
+  // writes output row `to` from the input rows ti with 0 <= to + p - ti*s <= k - 1.
+  void vocoder_context(int* left, int* right) const {
+    auto fdiv = [](long long x, long long y) { return x >= 0 ? x / y : -((-x + y - 1) / y); };  // floor, y > 0
+    auto conv = [](const ConvLayer& L, long long& a, long long& b) {
+      a -= L.pad;
+      b += (long long)(L.taps - 1) * L.dil - L.pad;
+    };
+    long long a = -(long long)((voc.post_k - 1) / 2), b = voc.hop - 1 + (voc.post_k - 1) / 2;
+    for (int i = (int)voc.ups.size() - 1; i >= 0; --i) {
+      long long lo = a, hi = b;
+      for (const auto& blk : voc.mrf[i]) {  // the resblocks read the same rows: the widest counts
+        long long ba = a, bb = b;
+        for (size_t q = blk.size(); q-- > 0;) {
+          conv(blk[q][1], ba, bb);
+          conv(blk[q][0], ba, bb);
+        }
+        lo = std::min(lo, ba);
+        hi = std::max(hi, bb);
+      }
+      const ConvLayer& U = voc.ups[i];
+      const long long s = U.up_s, k = (long long)U.taps * U.up_s, p = U.up_p;
+      a = -fdiv(-(lo + p - (k - 1)), s);  // ceil
+      b = fdiv(hi + p, s);
+    }
+    conv(voc.conv_pre, a, b);
+    *left = (int)-a;
+    *right = (int)b;
+  }
+
   void reserve_vocoder(int B, int T) {
     if (!voc.loaded) return;
     size_t per_frame = (size_t)voc.conv_pre.M;  // conv_pre output channels
@@ -860,6 +893,20 @@ int tts_vocoder_forward_chunk(tts_engine* eng, const float* d_mel, const int32_t
     HIP_CHECK(hipMemcpy2DAsync(d_wav, (size_t)T_chunk * hop * 4, eng->vchunk_wav + (size_t)ctx_left * hop,
                                (size_t)T_win * hop * 4, (size_t)T_chunk * hop * 4, B, hipMemcpyDeviceToDevice, s));
   });
+}
+
+int tts_vocoder_context(tts_engine* eng, int* left, int* right) {
+  try {  // host only: no device is selected and nothing is enqueued
+    if (!eng) throw TtsError(TTS_ERR_INVALID, "null engine");
+    if (!left || !right) throw TtsError(TTS_ERR_INVALID, "null left / right");
+    std::lock_guard<std::mutex> lk(eng->mu);
+    if (!eng->finalized || !eng->voc.loaded) throw TtsError(TTS_ERR_STATE, "vocoder weights not loaded/finalized");
+    eng->vocoder_context(left, right);
+    return TTS_OK;
+  } catch (const TtsError& e) {
+    g_last_error = e.what();
+    return e.code;
+  }
 }
 
 int tts_acoustic_forward_spk(tts_engine* eng, const int32_t* d_tokens, const int32_t* d_tok_lens, int B, int N,

@@ -73,6 +73,7 @@ C_API = [
     ("tts_engine_destroy", None, [_VP]),
     ("tts_vocoder_forward", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),
     ("tts_vocoder_forward_chunk", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    ("tts_vocoder_context", _I, [_VP, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ("tts_acoustic_forward", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP]),
     ("tts_acoustic_forward_spk", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP]),
     ("tts_acoustic_speaker_dim", _I, [_VP, ctypes.POINTER(ctypes.c_int)]),
@@ -322,6 +323,16 @@ class HipEngine:
                                                  ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)),
               "tts_vocoder_forward_chunk")
         return out
+
+    def vocoder_context(self):
+        """(left, right): mel frames of context a vocoder_chunk window needs around its chunk to
+        equal the whole-utterance pass -- the loaded generator's receptive field as the library
+        derives it from its packed layers (tts_vocoder_context; host only).  Equals
+        config.vocoder_context_frames of the loaded configuration."""
+        left, right = ctypes.c_int(), ctypes.c_int()
+        check(self.lib.tts_vocoder_context(self.handle, ctypes.byref(left), ctypes.byref(right)),
+              "tts_vocoder_context")
+        return left.value, right.value
 
     def resample(self, wav, lens, up: int, down: int, out=None, stream=None):
         """Per-utterance rational resampling on the device (scipy.signal.resample_poly(x, up,

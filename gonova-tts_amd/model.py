@@ -24,7 +24,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .config import AcousticConfig, VocoderConfig, SAMPLE_RATE
+from .config import AcousticConfig, VocoderConfig, SAMPLE_RATE, vocoder_context_frames
 from .engine import HipEngine, resample_chunk_counts, resample_history
 from .text import tokenize_batch
 from .weights import make_acoustic_weights, make_vocoder_weights
@@ -80,6 +80,8 @@ class GonovaTTS:
         self.engine = engine
         self.acoustic_cfg = acoustic_cfg
         self.vocoder_cfg = vocoder_cfg
+        # the generator's receptive field in mel frames (per side): what a streaming window carries
+        self.receptive_field = max(vocoder_context_frames(vocoder_cfg))
         # output rate: the vocoder's 22,050 Hz, or e.g. 24,000 for clients that assume the
         # reference's hard-coded rate (synthesizer.py:119); converted on the device
         # (tts_resample_poly, scipy.signal.resample_poly semantics)
@@ -122,7 +124,7 @@ class GonovaTTS:
     # -------------------------------------------------------------- synthesis
     def synthesize_tokens(self, tokens: np.ndarray, lens: np.ndarray, durations: Optional[np.ndarray] = None,
                           stream=None, speaker_embedding: Optional[np.ndarray] = None, host_lens: bool = True):
-        """tokens int32 [B, N], lens [B] -> (wav cuda float32 [B, T*256], wav_lens np.int64 [B]).
+        """tokens int32 [B, N], lens [B] -> (wav cuda float32 [B, T*hop], wav_lens np.int64 [B]).
         host_lens=False makes no host sync, so a caller can queue several batches back to back
         (dist.ShardedSynthesis), and returns (wav, wav_lens cuda int64 [B], pending): `pending` is
         None when nothing is left to check, else a PendingRange whose `word` the caller reads with
@@ -215,7 +217,27 @@ class GonovaTTS:
         return wav, h, tripped
 
     # -------------------------------------------------------------- streaming
-    STREAM_CONTEXT = 16  # mel frames of context per side; HiFi-GAN V1's receptive field is < 13
+    # fewest mel frames of context per side; HiFi-GAN V1's receptive field is exactly 13 frames
+    # (config.vocoder_context_frames).  A generator with a smaller hop needs more: stream_context.
+    STREAM_CONTEXT = 16
+
+    @property
+    def stream_context(self) -> int:
+        """Mel frames of context per side the streaming windows carry: the loaded generator's
+        receptive field (config.vocoder_context_frames; the engine derives the same pair from its
+        packed layers, HipEngine.vocoder_context), never fewer than STREAM_CONTEXT -- 16 for V1."""
+        return max(self.STREAM_CONTEXT, self.receptive_field)
+
+    def _context(self, context: Optional[int]) -> int:
+        """The context a stream runs with: stream_context, or the caller's when it covers the
+        receptive field (below it every chunk edge would carry a seam: ValueError)."""
+        if context is None:
+            return self.stream_context
+        rf = self.receptive_field
+        if int(context) < rf:
+            raise ValueError(f"stream context of {int(context)} frames is below the vocoder's receptive field "
+                             f"of {rf} frames")
+        return int(context)
 
     streams_resampled = True  # stream_tokens(output_rate=...) / stream_batch cut a resampled stream too
 
@@ -227,14 +249,19 @@ class GonovaTTS:
         With ctx >= the receptive field every kept sample is computed from the same inputs
         in the same order as the full-utterance pass, so the concatenated chunks equal it.
 
-        Yields (c0, wav_chunk cuda float32 [B, chunk*256], valid samples per utterance np [B]).
+        context None: stream_context, the loaded generator's receptive field (at least
+        STREAM_CONTEXT); a given context below the receptive field raises ValueError before any
+        GPU work.
+
+        Yields (c0, wav_chunk cuda float32 [B, chunk*hop], valid samples per utterance np [B]).
         output_rate None (or the vocoder's 22,050 Hz, whatever `sr` is): native chunks.  Another
         rate: every chunk goes through the chunked resampler (tts_resample_poly_chunk), which
         carries the filter's history between chunks; wav_chunk is then [B, cap] at that rate with
-        cap = ceil(chunk*256*up/down) + n_flush, and the valid counts differ from chunk to chunk
+        cap = ceil(chunk*hop*up/down) + n_flush, and the valid counts differ from chunk to chunk
         (an utterance's last chunk also brings the outputs held back until its end is known).  The
         valid parts concatenate to synthesize_tokens' output at that rate, bit for bit."""
         import torch
+        context = self._context(context)
         with torch.cuda.device(self.engine.device_index):  # (see synthesize_tokens)
             for c0, wav, valid, _ in self._stream_tokens(tokens, lens, chunk_frames, context, durations, stream,
                                                          speaker_embedding, output_rate):
@@ -245,7 +272,7 @@ class GonovaTTS:
         """stream_tokens' generator; yields a fourth item, ended np bool [B]: the utterance has no
         frame past this chunk."""
         import torch
-        ctx = self.STREAM_CONTEXT if context is None else context
+        ctx = self._context(context)
         dev = self.engine.torch_device
         B, N = tokens.shape
         hop = self.vocoder_cfg.hop

@@ -40,7 +40,8 @@ logger = logging.getLogger(__name__)
 
 
 # smallest sub-sentence frame (mel frames) a request gets: 2 x GonovaTTS.STREAM_CONTEXT, so a
-# chunk's window is at most half context
+# chunk's window is at most half context; a model whose generator needs more context
+# (GonovaTTS.stream_context, from its receptive field) raises the floor to twice that
 MIN_STREAM_FRAMES = 32
 
 
@@ -111,6 +112,7 @@ class TTSService:
         else:
             self.models = [await loop.run_in_executor(None, self.model_factory)]
         self.model = self.models[0]
+        self.stream_frames = self._stream_frames(self.stream_frames)  # the floor follows the model's context
         for m in self.models:
             for text in WARMUP_TEXTS:  # the reference's three warmups (synthesizer.py:197-207)
                 await loop.run_in_executor(None, m.generate_batch, [text])
@@ -144,12 +146,14 @@ class TTSService:
 
     def _stream_frames(self, v) -> int:
         """A request's (or the service default's) `stream_frames`: 0 = one frame per sentence;
-        otherwise at least `min_stream_frames`.  Each vocoder chunk runs a window of the chunk plus
-        2 x STREAM_CONTEXT frames and one device-to-host copy, so a tiny value (1 frame: a 33-frame
+        otherwise at least `min_stream_frames` and twice the model's `stream_context` (16 for a
+        model without the attribute).  Each vocoder chunk runs a window of the chunk plus
+        2 x stream_context frames and one device-to-host copy, so a tiny value (1 frame: a 33-frame
         window and a host sync per mel frame, ~860 chunks for a 10 s sentence) would let one
         request hold the shared batcher for every other connection; smaller values round up."""
         f = _frames(v)
-        return 0 if f == 0 else max(f, self.min_stream_frames)
+        floor = max(self.min_stream_frames, 2 * int(getattr(self.model, "stream_context", 16)))
+        return 0 if f == 0 else max(f, floor)
 
     async def _send_error(self, conn_id: str, message: str):
         ws = self.sockets.get(conn_id)

@@ -64,7 +64,8 @@ typedef struct tts_engine tts_engine;
  *   4  range guard of the exact encoder: tts_acoustic_range_flag / tts_acoustic_set_precision,
  *      TTS_ENCODER_F32
  *   5  tts_device_bytes (the library's device memory per HIP device); additive.  Also under 5,
- *      additive: tts_resample_poly_chunk / tts_resample_history (a caller detects them by symbol) */
+ *      additive: tts_resample_poly_chunk / tts_resample_history (a caller detects them by symbol),
+ *      and tts_vocoder_context (the loaded generator's receptive field in mel frames) */
 #define TTS_ABI_VERSION 5
 int tts_abi_version(void);
 
@@ -148,10 +149,19 @@ int tts_vocoder_forward(tts_engine* eng, const float* d_mel, const int32_t* d_me
 /* Streaming vocoder chunk with exact context: computes the waveform of frames
  * [ctx_left, ctx_left + T_chunk) of each d_mel[b] window [ctx_left + T_chunk + ctx_right][80]
  * (zero context at utterance edges is expressed by the caller passing shorter windows via
- * d_win_lens).  d_wav [B][T_chunk*256]. */
+ * d_win_lens).  d_wav [B][T_chunk*hop].  Any ctx_left is accepted (at an utterance's edge there
+ * is no context to pass); the chunk equals the whole-utterance pass when the window holds, on each
+ * side, the frames tts_vocoder_context reports or reaches the utterance's edge. */
 int tts_vocoder_forward_chunk(tts_engine* eng, const float* d_mel, const int32_t* d_win_lens,
                               int B, int T_win, int ctx_left, int T_chunk, float* d_wav,
                               void* stream);
+
+/* Host only: the loaded generator's receptive field in mel frames -> *left, *right, the frames
+ * of context before and after a chunk that tts_vocoder_forward_chunk needs to reproduce the
+ * whole-utterance pass.  Computed from the taps, dilations and strides of the layers finalize
+ * packed (13 and 13 for HiFi-GAN V1; it grows as the hop shrinks).  TTS_ERR_STATE before
+ * tts_engine_finalize or without a vocoder. */
+int tts_vocoder_context(tts_engine* eng, int* left, int* right);
 
 /* Acoustic model (replaces the text->spectrogram half of model.generate).
  *   d_tokens      [B][N] int32 token ids (padding ignored past d_tok_lens[b])
