@@ -616,32 +616,34 @@ __global__ __launch_bounds__(256, 1) void rel_attn_f32_kernel(const float* __res
 }
 
 // Merge of the key chunks (rel_attn_f32_kernel, kc > 0): O = sum_c 2^(m_c - M) O_c,
-// l = sum_c 2^(m_c - M) l_c, M = max_c m_c, out = O * (1 / l).  One thread per (row, 4 channels).
+// l = sum_c 2^(m_c - M) l_c, M = max_c m_c, out = O * (1 / l).  One thread per (row, 4 channels)
+// up to D = 384; a wider row (three heads and more) takes further rounds of 96 threads.
 template <int DK>
 __global__ __launch_bounds__(192) void rel_attn_merge_kernel(const float* __restrict__ po, const float* __restrict__ pml,
                                                             const int* __restrict__ lens, int Tp, int D, int H, int kc,
                                                             int nbatch, float* __restrict__ out) {
   const int r = blockIdx.x * 2 + threadIdx.x / 96;
-  const int c4 = threadIdx.x % 96;
-  if (4 * c4 >= D || r >= nbatch * Tp) return;
+  if (r >= nbatch * Tp) return;
   const int b = r / Tp, i = r - b * Tp;
   const int len = lens[b];
   if (i >= len) return;
-  const int h = 4 * c4 / DK, d = 4 * c4 - h * DK;
   const int n = (len + kc - 1) / kc;
-  auto prow = [&](int c) { return ((long long)(c * nbatch + b) * H + h) * Tp + i; };
-  float M = -INFINITY;
-  for (int c = 0; c < n; ++c) M = fmaxf(M, pml[2 * prow(c)]);
-  f32x4 o = f32x4{};
-  float l = 0.f;
-  for (int c = 0; c < n; ++c) {
-    const float2 ml = *reinterpret_cast<const float2*>(pml + 2 * prow(c));
-    const float wgt = at_exp2(ml.x - M);
-    o += *reinterpret_cast<const f32x4*>(po + prow(c) * DK + d) * wgt;
-    l += ml.y * wgt;
+  for (int c4 = threadIdx.x % 96; 4 * c4 < D; c4 += 96) {
+    const int h = 4 * c4 / DK, d = 4 * c4 - h * DK;
+    auto prow = [&](int c) { return ((long long)(c * nbatch + b) * H + h) * Tp + i; };
+    float M = -INFINITY;
+    for (int c = 0; c < n; ++c) M = fmaxf(M, pml[2 * prow(c)]);
+    f32x4 o = f32x4{};
+    float l = 0.f;
+    for (int c = 0; c < n; ++c) {
+      const float2 ml = *reinterpret_cast<const float2*>(pml + 2 * prow(c));
+      const float wgt = at_exp2(ml.x - M);
+      o += *reinterpret_cast<const f32x4*>(po + prow(c) * DK + d) * wgt;
+      l += ml.y * wgt;
+    }
+    const float inv = 1.f / l;
+    *reinterpret_cast<f32x4*>(out + (long long)r * D + h * DK + d) = o * inv;
   }
-  const float inv = 1.f / l;
-  *reinterpret_cast<f32x4*>(out + (long long)r * D + h * DK + d) = o * inv;
 }
 
 // Split-precision form (the fp32 encoder of a 16-bit model, acoustic.cpp): every fp32 operand

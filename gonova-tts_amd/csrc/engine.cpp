@@ -19,6 +19,7 @@
 
 #include "../../include/tts_hip.h"
 #include "acoustic.h"
+#include "acoustic_kernels.h"
 #include "switches.h"
 #include "common.h"
 #include "kernels.h"
@@ -1097,6 +1098,36 @@ int tts_op_conv1d(int dtype, const tts_conv_desc* d, void* stream) {
     p.up_s = d->up_s; p.up_cout = d->up_cout; p.up_p = d->up_p; p.up_len = d->up_len;
     p.B = d->B;
     launch_conv_checked(p, dtype, (hipStream_t)stream, nullptr, 0.0);
+    return TTS_OK;
+  } catch (const TtsError& e) {
+    g_last_error = e.what();
+    return e.code;
+  }
+}
+
+int64_t tts_op_rel_attn_ws_bytes(int B, int Tm, int Tp, int D, int H) {
+  if (B <= 0 || Tm <= 0 || Tp < Tm || D <= 0 || H <= 0) return 0;
+  return rel_attn_f32_ws_bytes(B, Tm, Tp, D, H);
+}
+
+int tts_op_rel_attn(int dtype, int split, const float* pos_u, const float* pos_v, const void* qkv, const void* ptab,
+                    const int32_t* lens, int B, int Tm, int Tp, int D, int H, int rmax, float scale, void* out,
+                    int32_t* range_flag, void* ws, int64_t ws_bytes, void* stream) {
+  try {
+    if (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_BF16) throw TtsError(TTS_ERR_INVALID, "rel_attn: bad dtype");
+    if (split && dtype != DT_F32) throw TtsError(TTS_ERR_INVALID, "rel_attn: the split form takes fp32 operands");
+    if (!pos_u || !pos_v || !qkv || !ptab || !lens || !out) throw TtsError(TTS_ERR_INVALID, "rel_attn: null buffer");
+    if (B <= 0 || Tm <= 0 || Tp < Tm)
+      throw TtsError(TTS_ERR_INVALID, "rel_attn: needs B > 0 and 0 < Tm <= Tp (B " + std::to_string(B) + ", Tm " +
+                                          std::to_string(Tm) + ", Tp " + std::to_string(Tp) + ")");
+    if (rmax < Tm)
+      throw TtsError(TTS_ERR_INVALID, "rel_attn: position table of rmax " + std::to_string(rmax) + " below Tm " + std::to_string(Tm));
+    if (H <= 0 || D <= 0 || !rel_attn_supported(dtype, D, H))
+      throw TtsError(TTS_ERR_INVALID, "rel_attn: D " + std::to_string(D) + " / H " + std::to_string(H) +
+                                          " is not a head size the fused attention takes (192)");
+    if (ws_bytes < 0 || (ws_bytes > 0 && !ws)) throw TtsError(TTS_ERR_INVALID, "rel_attn: bad workspace");
+    HIP_CHECK(launch_rel_attn(dtype, split != 0, pos_u, pos_v, qkv, ptab, lens, B, Tm, Tp, D, H, rmax, scale, out,
+                              (hipStream_t)stream, range_flag, (float*)ws, ws_bytes));
     return TTS_OK;
   } catch (const TtsError& e) {
     g_last_error = e.what();

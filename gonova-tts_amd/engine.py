@@ -93,6 +93,9 @@ C_API = [
     ("tts_get_switch", _I, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
     ("tts_last_error", ctypes.c_char_p, []),
     ("tts_op_conv1d", _I, [_I, ctypes.POINTER(TtsConvDesc), _VP]),
+    ("tts_op_rel_attn", _I, [_I, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _F, _VP, _VP, _VP,
+                             ctypes.c_int64, _VP]),
+    ("tts_op_rel_attn_ws_bytes", ctypes.c_int64, [_I, _I, _I, _I, _I]),
 ]
 
 _lib = None
@@ -488,3 +491,27 @@ class HipEngine:
 def conv1d_op(dtype: str, desc: TtsConvDesc, stream=None):
     lib = load_library()
     check(lib.tts_op_conv1d(DTYPES[dtype], ctypes.byref(desc), _stream_ptr(stream)), "tts_op_conv1d")
+
+
+def rel_attn_ws_bytes(B: int, Tm: int, Tp: int, D: int, H: int) -> int:
+    """Host only: workspace bytes of the fp32 attention's key chunks (tts_op_rel_attn_ws_bytes)."""
+    return int(load_library().tts_op_rel_attn_ws_bytes(B, Tm, Tp, D, H))
+
+
+def rel_attn_op(dtype: str, pos_u, pos_v, qkv, ptab, lens, Tm: int, rmax: int, scale: float, out, split: bool = False,
+                range_flag=None, ws=None, stream=None):
+    """One fused relative-position attention launch on torch device tensors (include/tts_hip.h
+    tts_op_rel_attn): pos_u / pos_v [H, 192] f32, qkv [B, Tp, 3D], ptab [2 rmax, D], lens [B] int32,
+    out [B, Tp, D] (written in place below each length), range_flag an int32 tensor or None, ws a
+    workspace tensor or None."""
+    lib = load_library()
+    B, Tp, D3 = qkv.shape
+    H = pos_u.shape[0]
+    for t in (pos_u, pos_v, qkv, ptab, lens, out):
+        assert t.is_contiguous()
+    assert tuple(out.shape) == (B, Tp, D3 // 3) and tuple(ptab.shape) == (2 * rmax, D3 // 3)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    check(lib.tts_op_rel_attn(DTYPES[dtype], int(split), vp(pos_u), vp(pos_v), vp(qkv), vp(ptab), vp(lens), B, Tm, Tp,
+                              D3 // 3, H, rmax, float(scale), vp(out), vp(range_flag), vp(ws),
+                              ws.numel() * ws.element_size() if ws is not None else 0, _stream_ptr(stream)),
+          "tts_op_rel_attn")

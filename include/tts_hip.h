@@ -65,7 +65,8 @@ typedef struct tts_engine tts_engine;
  *      TTS_ENCODER_F32
  *   5  tts_device_bytes (the library's device memory per HIP device); additive.  Also under 5,
  *      additive: tts_resample_poly_chunk / tts_resample_history (a caller detects them by symbol),
- *      and tts_vocoder_context (the loaded generator's receptive field in mel frames) */
+ *      and tts_vocoder_context (the loaded generator's receptive field in mel frames), and the
+ *      op-level tts_op_rel_attn / tts_op_rel_attn_ws_bytes */
 #define TTS_ABI_VERSION 5
 int tts_abi_version(void);
 
@@ -278,6 +279,36 @@ typedef struct tts_conv_desc {
 } tts_conv_desc;
 
 int tts_op_conv1d(int dtype, const tts_conv_desc* desc, void* stream);
+
+/* ---- op-level entry used by the parity tests (one fused relative-position attention) ----
+ * (ABI 5, additive; a caller detects it by symbol.)  For utterance b, head h, query i < lens[b]:
+ *   S[i][j]  = ((q[i] + pos_u[h]) . k[j] + (q[i] + pos_v[h]) . R[i - j]) * scale,   j < lens[b]
+ *   out[b][i][h*192 ..] = softmax_j(S[i]) . v
+ * with q / k / v the three D-wide slices of qkv row [b][i] and R[rel] = ptab row rmax - 1 - rel.
+ *   dtype      TTS_DTYPE_*: the type of qkv, ptab and out.  split (fp32 only): every product as
+ *              three f16 MFMAs (the exact encoder's form); operands must stay inside f16's range
+ *   pos_u/v    [H][192] float32; q + pos is one fp32 add, rounded once to dtype
+ *   qkv        [B][Tp][3*D], ptab [2*rmax][D], out [B][Tp][D], lens [B] int32 with lens[b] <= Tm
+ *   Tm <= Tp, Tm <= rmax, D == H * 192; anything else is TTS_ERR_INVALID with a message
+ *   range_flag optional device int32: the split form ORs 1 into it when the f16 high half of an
+ *              operand it staged is inf or NaN (tts_acoustic_range_flag's word); never cleared here
+ *   ws         optional caller-owned device workspace of ws_bytes for the fp32 (non-split) form's
+ *              key chunks; with fewer than tts_op_rel_attn_ws_bytes() the kernel runs one chunk
+ * Rows at or past an utterance's length:
+ *   out   rows i >= lens[b] are never written (an utterance of length 0 writes nothing).
+ *   qkv   the k and v slices of rows j >= lens[b] never reach a sum: the 16-bit and split forms do
+ *         not read them, the fp32 form reads rows < Tp and replaces them with zeros.  The q slices
+ *         of rows up to the end of the last 64-query tile (clamped to row Tp - 1) are read as
+ *         queries whose results are discarded; they stay private to their own row, so any value is
+ *         harmless there, except that the split form range-checks them like every operand.
+ * A row's bits depend on its own utterance only, never on B or on the other utterances.
+ * TTS_ATTN_KSPLIT (16-bit) and TTS_ATTN_F32_KC (fp32) select the alternative forms as in the model. */
+int tts_op_rel_attn(int dtype, int split, const float* pos_u, const float* pos_v, const void* qkv,
+                    const void* ptab, const int32_t* lens, int B, int Tm, int Tp, int D, int H, int rmax,
+                    float scale, void* out, int32_t* range_flag, void* ws, int64_t ws_bytes, void* stream);
+/* Host only: bytes of workspace the fp32 form's key chunks need at these extents under the current
+ * TTS_ATTN_F32_KC (0: none, one chunk covers Tm). */
+int64_t tts_op_rel_attn_ws_bytes(int B, int Tm, int Tp, int D, int H);
 
 #ifdef __cplusplus
 }
