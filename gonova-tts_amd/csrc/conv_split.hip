@@ -4,15 +4,17 @@
 // 16-bit rate.  An fp32 value a is split into two f16 terms,
 //     a_hi = f16(a),   a_lo = f16(a - a_hi)        (a ~= a_hi + a_lo),
 // a_hi carrying the top 11 significand bits and a_lo the next 11 (a_lo is subnormal for |a| below
-// ~2^-3 and then keeps fewer bits: an absolute error under 2^-25 per element, below the fp32
-// rounding of the sums it enters), and
+// ~2^-3 and then keeps fewer bits: an absolute error under 2^-25 per element -- activations are
+// not scaled, so a product of such an element is off by up to 2^-25 |w| whatever |a| is; the
+// error model is written out at tts_op_conv1d_ex in include/tts_hip.h), and
 //     sum a*b ~= sum a_hi*b_hi + a_hi*b_lo + a_lo*b_hi
 // runs as three v_mfma_f32_32x32x16_f16 into ONE fp32 accumulator.  The weights are stored scaled
 // by a power of two 2^s per layer (frag_pack_split: max|w| 2^s in [2^14, 2^15), so the weights' lo
 // plane stays normal) and the sums are multiplied by ConvParams::w_unscale = 2^-s, exactly.  The
-// dropped a_lo*b_lo term and the representation errors are ~2^-21 relative per product: ~8x the
-// fp32 rounding of one product, 1000x below bf16.  Effective fp32 throughput is 1/3 of the f16
-// peak: ~5x the native fp32 MFMA.  Range: |a| < 65504 (f16); the encoder's activations are O(100).
+// dropped a_lo*b_lo term and the representation errors are ~2^-21 relative per product (while
+// a_lo is a normal f16, |a| above ~2^-3): ~8x the fp32 rounding of one product, 1000x below bf16.
+// Effective fp32 throughput is 1/3 of the f16 peak: ~5x the native fp32 MFMA.  Range: |a| < 65504
+// (f16); the encoder's activations are O(100).
 //
 // Used for the acoustic encoder + variance predictors in "exact" encoder precision (the
 // integer durations of HF:181-183 then match the fp32 oracle, SURVEY.md §8c "durations: exact
@@ -527,7 +529,10 @@ __global__ __launch_bounds__(256, 2) void conv_splitp_kernel(ConvParams p, int C
       // stays unconditional, not sunk into a branch with a wait of its own)
       const int L = __builtin_amdgcn_raw_buffer_load_b32(lrs, b * 4, 0, 0) | (p.x_len ? 0 : 0x7fffffff);
       const int lim = min(L, p.x_rows);
-      m |= (f >= 0 && f < F && r < lim ? 1 : 0) << i;
+      // (a register past the tile's R rows holds a copy of row R - 1 -- load_x_to clamps -- which is
+      // never stored but is range-checked with this bit: without the last term a valid row past the
+      // tile lent its bit to a masked row's contents, and garbage in the padding raised the range word)
+      m |= (f >= 0 && f < F && r < lim && r0 + i * rstep < R ? 1 : 0) << i;
     }
     return m;
   };

@@ -38,6 +38,13 @@ struct HostTensor {
 
 }  // namespace
 
+// op-level conv layer (tts_op_conv_layer_create): one make_conv result and the buffers it owns
+struct tts_conv_layer {
+  int dtype = DT_F32;
+  ConvLayer layer;
+  std::vector<void*> allocs;
+};
+
 struct VocoderWeights {
   bool loaded = false;
   float* mean = nullptr;
@@ -1098,6 +1105,91 @@ int tts_op_conv1d(int dtype, const tts_conv_desc* d, void* stream) {
     p.up_s = d->up_s; p.up_cout = d->up_cout; p.up_p = d->up_p; p.up_len = d->up_len;
     p.B = d->B;
     launch_conv_checked(p, dtype, (hipStream_t)stream, nullptr, 0.0);
+    return TTS_OK;
+  } catch (const TtsError& e) {
+    g_last_error = e.what();
+    return e.code;
+  }
+}
+
+int tts_op_conv_layer_create(int dtype, int split, const float* w, const float* bias, int M, int Cin, int k, int dil,
+                             int pad, tts_conv_layer** layer) {
+  try {
+    if (!layer) throw TtsError(TTS_ERR_INVALID, "conv layer: null out pointer");
+    *layer = nullptr;
+    if (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_BF16) throw TtsError(TTS_ERR_INVALID, "conv layer: bad dtype");
+    if (split && dtype != DT_F32) throw TtsError(TTS_ERR_INVALID, "conv layer: the split form takes an fp32 layer");
+    if (!w || M <= 0 || Cin <= 0 || k <= 0 || dil <= 0 || pad < 0)
+      throw TtsError(TTS_ERR_INVALID, "conv layer: bad dims");
+    const std::vector<float> wv(w, w + (size_t)M * Cin * k);
+    const std::vector<float> bv = bias ? std::vector<float>(bias, bias + M) : std::vector<float>();
+    auto* L = new tts_conv_layer;
+    L->dtype = dtype;
+    try {
+      L->layer = make_conv(wv, M, Cin, k, bv, dil, pad, dtype, L->allocs, nullptr, split != 0);  // finalize's packing
+    } catch (...) {
+      for (void* p : L->allocs) (void)dev_free(p);
+      delete L;
+      throw;
+    }
+    *layer = L;
+    return TTS_OK;
+  } catch (const TtsError& e) {
+    g_last_error = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return TTS_ERR_INVALID;
+  }
+}
+
+void tts_op_conv_layer_destroy(tts_conv_layer* layer) {
+  if (!layer) return;
+  for (void* p : layer->allocs) (void)dev_free(p);
+  delete layer;
+}
+
+int64_t tts_op_conv_ws_bytes(int taps, int Cin, int M, int rows) {
+  if (taps <= 0 || Cin <= 0 || M <= 0 || rows <= 0) return 0;
+  return std::max(conv_split_ws_bytes(taps, Cin, M, rows), f32_splitk_ws_bytes(taps, Cin, M, rows));
+}
+
+int tts_op_conv1d_ex(const tts_conv_layer* layer, const tts_conv_desc* d, tts_conv_ext* x, void* stream) {
+  try {
+    if (!layer || !d) throw TtsError(TTS_ERR_INVALID, "conv1d_ex: null layer or desc");
+    if (d->up_s) throw TtsError(TTS_ERR_INVALID, "conv1d_ex: the transposed-conv mapping (up_s) is not taken here");
+    if (!d->x || !d->y || d->B <= 0) throw TtsError(TTS_ERR_INVALID, "conv1d_ex: null buffer or empty batch");
+    const ConvLayer& L = layer->layer;
+    ConvParams p = conv_params_default();
+    p.x = d->x; p.sxb = d->sxb; p.sxr = d->sxr; p.x_len = d->x_len; p.x_rows = d->x_rows;
+    p.w = L.w; p.swb = 0; p.w_ld = L.taps * L.Cin; p.bias = L.bias; p.wpk = L.wpk; p.w_unscale = L.wpk_unscale;
+    p.y = d->y; p.syb = d->syb; p.syr = d->syr;
+    p.r1 = d->r1; p.r2 = d->r2; p.srb = d->srb; p.srr = d->srr;
+    p.y_len = d->y_len; p.y_rows = d->y_rows;
+    p.M = L.M; p.Cin = L.Cin; p.taps = L.taps; p.dil = L.dil; p.pad = L.pad;
+    p.in_slope = d->in_slope; p.act_out = d->act_out; p.out_slope = d->out_slope;
+    p.alpha = d->alpha; p.out_scale = d->out_scale;
+    p.B = d->B;
+    if (x) {
+      if (x->rows_pad < 0 || x->ws_bytes < 0 || (x->ws_bytes > 0 && !x->ws) || x->ln_cnt_n < 0 || (x->ln_cnt_n > 0 && !x->ln_cnt))
+        throw TtsError(TTS_ERR_INVALID, "conv1d_ex: bad rows_pad / workspace / counters");
+      if ((x->ln_out || x->ln_lin_out) && (!x->ln_g1 || !x->ln_b1))
+        throw TtsError(TTS_ERR_INVALID, "conv1d_ex: a LayerNorm needs ln_g1 and ln_b1");
+      if ((x->ln_g2 != nullptr) != (x->ln_b2 != nullptr))
+        throw TtsError(TTS_ERR_INVALID, "conv1d_ex: ln_g2 and ln_b2 come together");
+      if (x->ln_lin_out && (!x->ln_lin_w || x->ln_out || x->ln_g2))
+        throw TtsError(TTS_ERR_INVALID, "conv1d_ex: ln_lin_out takes ln_lin_w, one LayerNorm and no ln_out");
+      p.rows_pad = x->rows_pad; p.ws = (float*)x->ws; p.ws_bytes = x->ws ? x->ws_bytes : 0;
+      p.f32_splitk = x->f32_splitk; p.no_split = x->no_split; p.range_flag = x->range_flag;
+      p.ln_out = x->ln_out; p.ln_g1 = x->ln_g1; p.ln_b1 = x->ln_b1; p.ln_g2 = x->ln_g2; p.ln_b2 = x->ln_b2;
+      p.ln_eps = x->ln_eps; p.ln_cnt = x->ln_cnt_n > 0 ? x->ln_cnt : nullptr; p.ln_cnt_n = x->ln_cnt_n;
+      p.ln_lin_w = x->ln_lin_w; p.ln_lin_b = x->ln_lin_b; p.ln_lin_out = x->ln_lin_out;
+    }
+    launch_conv_checked(p, layer->dtype, (hipStream_t)stream, nullptr, 0.0);
+    if (x) {
+      x->kind = conv_gemm_kind(layer->dtype, p);
+      x->kernels = conv_last_kernels();
+    }
     return TTS_OK;
   } catch (const TtsError& e) {
     g_last_error = e.what();

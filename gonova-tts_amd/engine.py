@@ -59,6 +59,19 @@ class TtsConvDesc(ctypes.Structure):
     ]
 
 
+class TtsConvExt(ctypes.Structure):
+    """tts_conv_ext: the launch fields tts_conv_desc lacks; kind / kernels are outputs."""
+    _fields_ = [
+        ("rows_pad", ctypes.c_int32), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64),
+        ("f32_splitk", ctypes.c_int32), ("no_split", ctypes.c_int32), ("range_flag", ctypes.c_void_p),
+        ("ln_out", ctypes.c_void_p), ("ln_g1", ctypes.c_void_p), ("ln_b1", ctypes.c_void_p),
+        ("ln_g2", ctypes.c_void_p), ("ln_b2", ctypes.c_void_p), ("ln_eps", ctypes.c_float),
+        ("ln_cnt", ctypes.c_void_p), ("ln_cnt_n", ctypes.c_int32),
+        ("ln_lin_w", ctypes.c_void_p), ("ln_lin_b", ctypes.c_float), ("ln_lin_out", ctypes.c_void_p),
+        ("kind", ctypes.c_int32), ("kernels", ctypes.c_int32),
+    ]
+
+
 # every function declared in include/tts_hip.h: (name, restype, argtypes)
 _VP, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 C_API = [
@@ -96,6 +109,10 @@ C_API = [
     ("tts_op_rel_attn", _I, [_I, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _F, _VP, _VP, _VP,
                              ctypes.c_int64, _VP]),
     ("tts_op_rel_attn_ws_bytes", ctypes.c_int64, [_I, _I, _I, _I, _I]),
+    ("tts_op_conv_layer_create", _I, [_I, _I, _VP, _VP, _I, _I, _I, _I, _I, ctypes.POINTER(_VP)]),
+    ("tts_op_conv_layer_destroy", None, [_VP]),
+    ("tts_op_conv1d_ex", _I, [_VP, ctypes.POINTER(TtsConvDesc), ctypes.POINTER(TtsConvExt), _VP]),
+    ("tts_op_conv_ws_bytes", ctypes.c_int64, [_I, _I, _I, _I]),
 ]
 
 _lib = None
@@ -491,6 +508,52 @@ class HipEngine:
 def conv1d_op(dtype: str, desc: TtsConvDesc, stream=None):
     lib = load_library()
     check(lib.tts_op_conv1d(DTYPES[dtype], ctypes.byref(desc), _stream_ptr(stream)), "tts_op_conv1d")
+
+
+class ConvLayerOp:
+    """One conv layer packed as finalize packs it (tts_op_conv_layer_create: make_conv, so the
+    fragment / split-precision copies and the weight scale are the models' own).  w is host fp32
+    in nn.Conv1d layout [M, Cin, k]; split (fp32 only) also builds the split-precision copy."""
+
+    def __init__(self, dtype: str, w, bias=None, dil: int = 1, pad: int = 0, split: bool = False):
+        lib = load_library()
+        w = np.ascontiguousarray(w, np.float32)
+        self.M, self.Cin, self.k = (int(v) for v in w.shape)
+        self.dil, self.pad, self.dtype, self.split = int(dil), int(pad), dtype, bool(split)
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        assert b is None or b.shape == (self.M,)
+        h = ctypes.c_void_p()
+        check(lib.tts_op_conv_layer_create(DTYPES[dtype], int(self.split), w.ctypes.data_as(ctypes.c_void_p),
+                                           None if b is None else b.ctypes.data_as(ctypes.c_void_p), self.M, self.Cin,
+                                           self.k, self.dil, self.pad, ctypes.byref(h)), "tts_op_conv_layer_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().tts_op_conv_layer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def conv_ws_bytes(taps: int, Cin: int, M: int, rows: int) -> int:
+    """Host only: split-K workspace bytes a launch of this shape over `rows` flat rows can use
+    (tts_op_conv_ws_bytes: the larger of the packed split form's and the fp32 split-K's)."""
+    return int(load_library().tts_op_conv_ws_bytes(taps, Cin, M, rows))
+
+
+def conv1d_ex_op(layer: ConvLayerOp, desc: TtsConvDesc, ext: Optional[TtsConvExt] = None, stream=None):
+    """One launch of a packed layer through launch_conv_checked (tts_op_conv1d_ex); the layer's
+    fields of desc are ignored.  -> (kind, kernels): the family index of profile_read_kinds and the
+    kernels enqueued (the GEMM, a split-K reduce, a separate LayerNorm)."""
+    lib = load_library()
+    ext = ext if ext is not None else TtsConvExt()
+    check(lib.tts_op_conv1d_ex(layer._h, ctypes.byref(desc), ctypes.byref(ext), _stream_ptr(stream)), "tts_op_conv1d_ex")
+    return int(ext.kind), int(ext.kernels)
 
 
 def rel_attn_ws_bytes(B: int, Tm: int, Tp: int, D: int, H: int) -> int:

@@ -66,7 +66,8 @@ typedef struct tts_engine tts_engine;
  *   5  tts_device_bytes (the library's device memory per HIP device); additive.  Also under 5,
  *      additive: tts_resample_poly_chunk / tts_resample_history (a caller detects them by symbol),
  *      and tts_vocoder_context (the loaded generator's receptive field in mel frames), and the
- *      op-level tts_op_rel_attn / tts_op_rel_attn_ws_bytes */
+ *      op-level tts_op_rel_attn / tts_op_rel_attn_ws_bytes, and the op-level
+ *      tts_op_conv_layer_create / _destroy / tts_op_conv1d_ex / tts_op_conv_ws_bytes */
 #define TTS_ABI_VERSION 5
 int tts_abi_version(void);
 
@@ -84,7 +85,8 @@ typedef struct tts_config {
 
 /* Acoustic encoder precision.  EXACT (the default, 0): with a 16-bit acoustic_dtype the encoder,
  * speaker projection and variance predictors keep fp32 activations and run their GEMMs as three
- * f16 MFMAs (~2^-21 relative per product), so the predicted integer durations
+ * f16 MFMAs (~2^-21 relative per product for activations above ~2^-3, an absolute 2^-25 |w| below:
+ * tts_op_conv1d_ex's error model), so the predicted integer durations
  * clamp(round(exp(x) - 1), 0) (HF:181-183) match an fp32 evaluation; the decoder and postnet run in
  * acoustic_dtype.  FAST (1): the whole acoustic model runs in acoustic_dtype (durations can
  * round differently near .5).  With acoustic_dtype = F32, EXACT runs the encoder side on the same
@@ -105,7 +107,7 @@ enum { TTS_ENCODER_EXACT = 0, TTS_ENCODER_FAST = 1, TTS_ENCODER_F32 = 2 };
  * (tts_acoustic_set_precision), not a tts_config value. */
 
 /* fp32 vocoders (vocoder_dtype = TTS_DTYPE_F32): the resblock convs of every stage (channel counts
- * divisible by 32, >= 32) run as split-precision GEMMs (three f16 MFMAs per product, ~2^-21 relative, like the exact
+ * divisible by 32, >= 32) run as split-precision GEMMs (three f16 MFMAs per product, ~2^-21 relative above |x| ~ 2^-3, like the exact
  * encoder).  tts_vocoder_forward / _chunk then read the layers' range word once at the end of the
  * call (one sync of `stream`) and, if an activation left f16's range, rerun the forward with every
  * layer on the fp32 MFMA path; 16-bit vocoders are unaffected and stay asynchronous. */
@@ -279,6 +281,81 @@ typedef struct tts_conv_desc {
 } tts_conv_desc;
 
 int tts_op_conv1d(int dtype, const tts_conv_desc* desc, void* stream);
+
+/* ---- op-level entry that reaches every conv GEMM form (ABI 5, additive; detected by symbol) ----
+ * tts_op_conv1d above can only run conv_gemm_kernel.  Here the layer is packed as the engine packs
+ * it at finalize (make_conv: the [M][taps][Cin] copy, the fragment-packed copy of a 16-bit layer
+ * with Cin % 64 == 0 and M >= 64, and for an fp32 layer with split != 0 the two-plane f16 copy at a
+ * power-of-two scale with its unscale factor), and the launch carries every field the models set.
+ *   w     host fp32 in nn.Conv1d layout [M][Cin][k]; bias host fp32 [M] or NULL (zeros)
+ *   split fp32 only: also build the split-precision copy (three f16 MFMAs per product)
+ * The layer lives on the HIP device current at create; destroy frees its buffers (NULL is fine). */
+typedef struct tts_conv_layer tts_conv_layer;
+int tts_op_conv_layer_create(int dtype, int split, const float* w, const float* bias, int M, int Cin, int k,
+                             int dil, int pad, tts_conv_layer** layer);
+void tts_op_conv_layer_destroy(tts_conv_layer* layer);
+
+/* Everything of a launch that tts_conv_desc does not hold.  All-zero = the plain launch. */
+typedef struct tts_conv_ext {
+  int32_t rows_pad;      /* > 0: the packed-row promise -- x / y / residuals contiguous [B][rows][C], x_rows ==
+                            y_rows a multiple of 32, every utterance followed by >= rows_pad masked rows */
+  void* ws;              /* fp32 split-K partials (either split-K form), ws_bytes of them; see */
+  int64_t ws_bytes;      /* tts_op_conv_ws_bytes.  Without it the packed split form runs one slice. */
+  int32_t f32_splitk;    /* fp32 MFMA form (no split copy, or no_split): split K into slices + a reduce */
+  int32_t no_split;      /* run an fp32 layer on the fp32 MFMA kernel even where the split form is eligible */
+  int32_t* range_flag;   /* device int32 or NULL: the split form ORs 1 into it when the f16 high half of an
+                            activation it staged is inf or NaN (|x| >= 65520); never cleared here */
+  void* ln_out;          /* LN2?(LN1(y)) rows, y's strides and dtype (NULL: no LayerNorm) */
+  const float *ln_g1, *ln_b1, *ln_g2, *ln_b2;  /* device fp32 [M]; ln_g2 NULL: one LayerNorm */
+  float ln_eps;
+  int32_t* ln_cnt;       /* device int32 [ln_cnt_n] row-tile counters for the in-launch LayerNorm, or NULL */
+  int32_t ln_cnt_n;
+  const float* ln_lin_w; /* with ln_lin_out: LN1(y) . ln_lin_w + ln_lin_b per row (fp32 [B][y_rows]) instead */
+  float ln_lin_b;        /* of ln_out */
+  float* ln_lin_out;
+  int32_t kind;          /* out: the family the launch ran as (tts_engine_profile_read_kinds' index) */
+  int32_t kernels;       /* out: kernels enqueued (the GEMM, + a split-K reduce, + a separate LayerNorm) */
+} tts_conv_ext;
+
+/* One conv launch of `layer`: desc's w / swb / w_ld / bias / M / Cin / taps / dil / pad are taken from
+ * the layer (what desc holds there is ignored), the transposed-conv mapping (up_s) must be 0, ext
+ * may be NULL.  Validated like every model launch (TTS_ERR_INVALID with a message).
+ *
+ * With len = min(y_len[b], y_rows) (y_rows when y_len is NULL), rows r >= len of utterance b:
+ *   y           never written, by any family: conv_gemm_kernel, conv_xres_kernel, both split-precision
+ *               kernels and split_reduce_kernel all skip them (a caller that needs zeros there clears
+ *               y itself).  Where a split-K reduce applies the LayerNorm (split_reduce_ln_kernel:
+ *               ln_out given, no act_out, M <= 512) y is not written at all, valid rows included.
+ *   ln_out      never written: the in-launch tails, split_reduce_ln_kernel and the separate LayerNorm
+ *               launch all skip them.
+ *   ln_lin_out  the families differ: a launch that applies the LayerNorm itself (ln_cnt given, grid
+ *               large enough or TTS_LN_FUSE=7) leaves them alone; the separate LayerNorm + Linear launch
+ *               writes every row of [B][y_rows], those past len from whatever y holds there.
+ * An utterance of length 0 writes nothing (ln_lin_out as above).
+ * x rows at or past x_len[b] (x_rows when NULL), rows before the utterance (the left pad) and the pad
+ * rows of the packed layout never reach a sum: every kernel replaces them with zeros as it stages
+ * them, whatever they hold (NaN and inf included), before the split form's range check, so they
+ * never reach the range word either.
+ * ln_cnt must be all zero on entry; a launch that used the counters leaves them all zero again (the
+ * last M block of a row tile resets its counter), so they serve the next launch on the stream.
+ * A row's bits depend on its own utterance only -- not on B, on the other utterances, or on the row
+ * tile height the grid picked (the K order comes from the layer shape alone).
+ *
+ * Error of the split-precision form (fp32 layer, split != 0).  Each fp32 operand is held as two f16
+ * halves; the weights are scaled by a power of two per layer, so their low halves stay normal f16
+ * down to ~2^-19 max|w|; the activations are NOT scaled.  A product x.w is hi.hi + hi.lo + lo.hi in
+ * one fp32 accumulator: the dropped lo.lo term and the two low halves' roundings cost at most
+ * 3 * 2^-22 |x||w| while x's low half is a normal f16, i.e. for |x| above ~2^-3.  Below that the low
+ * half is a subnormal (spacing 2^-24) and a product is off by up to 2^-25 |w| whatever |x| is: an
+ * absolute floor, ~2^-15 relative at |x| = 1e-3 (measured on an MI355X with activations of
+ * 2..4 * 2^-12: up to 64 * 2^-21 of sum|x||w|, against 0.5 * 2^-21 at |x| ~ 1; profiles/conv_op_parity.json).
+ * The same floor, 2^-25 2^-s |x|, holds for a weight under ~2^-19 of its layer's largest.  The
+ * models feed these layers LayerNorm outputs of order one; tests/test_conv_op_gpu.py holds every
+ * form to this model (oracle/conv.py), the small activations included. */
+int tts_op_conv1d_ex(const tts_conv_layer* layer, const tts_conv_desc* desc, tts_conv_ext* ext, void* stream);
+/* Host only: bytes of split-K workspace a launch of this shape over `rows` (= B * y_rows) flat rows
+ * can use -- the larger of the packed split form's and the fp32 split-K's partials (0: neither splits). */
+int64_t tts_op_conv_ws_bytes(int taps, int Cin, int M, int rows);
 
 /* ---- op-level entry used by the parity tests (one fused relative-position attention) ----
  * (ABI 5, additive; a caller detects it by symbol.)  For utterance b, head h, query i < lens[b]:
