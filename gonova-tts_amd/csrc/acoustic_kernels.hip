@@ -13,6 +13,17 @@
 
 namespace tts {
 
+// An fp32 result rounded to T.  Without the barrier the compiler may fold an fp32 multiply and the
+// conversion into one v_fma_mixlo_f16 -- a single rounding of the exact product to f16, other bits
+// than fp32-then-f16 -- and does so in some instances only (ln_rows.h ln_batch): the f16 embed and
+// both f16 regulate kernels were such instances, so their bits were not the "one fp32 multiply,
+// one rounding" include/tts_hip.h states (tests/test_rowwise_op_gpu.py test_regulate, fp32 -> f16).
+template <typename T>
+__device__ inline T round_from_f32(float v) {
+  asm volatile("" : "+v"(v));
+  return from_f32<T>(v);
+}
+
 // ---------------------------------------------------------------------------
 // token embedding * sqrt(D)   (HF:793-795 embed, HF:763 input_scale)
 // ---------------------------------------------------------------------------
@@ -30,7 +41,7 @@ __global__ void embed_kernel(const int* __restrict__ ids, const int* __restrict_
   int id = ids[(long long)b * N + t];
   id = min(max(id, 0), V - 1);
   const T* e = E + (long long)id * D;
-  for (int c = threadIdx.x; c < D; c += blockDim.x) o[c] = from_f32<T>(to_f32(e[c]) * scale);
+  for (int c = threadIdx.x; c < D; c += blockDim.x) o[c] = round_from_f32<T>(to_f32(e[c]) * scale);
 }
 
 // ---------------------------------------------------------------------------
@@ -463,7 +474,7 @@ __global__ void regulate_kernel(const TI* __restrict__ enc, int N, int D, const 
     return;
   }
   const TI* s = enc + ((long long)b * N + tok) * D;
-  for (int c = threadIdx.x; c < D; c += blockDim.x) o[c] = from_f32<T>(to_f32(s[c]) * scale);
+  for (int c = threadIdx.x; c < D; c += blockDim.x) o[c] = round_from_f32<T>(to_f32(s[c]) * scale);
 }
 
 // mel [B][Tin][C] (T, row stride Tin >= mel_len) -> float32 [B][Tcap][C], rows >= mel_len zeroed

@@ -1227,4 +1227,205 @@ int tts_op_rel_attn(int dtype, int split, const float* pos_u, const float* pos_v
   }
 }
 
+// ---- op-level entries of the acoustic model's row-wise kernels (acoustic_kernels.hip) ----
+// Each validates what its launcher assumes and its kernel would otherwise read or write out of
+// bounds on, then enqueues the one launch the model makes.
+}  // extern "C"
+
+namespace {
+
+void op_require(bool ok, const char* op, const std::string& what) {
+  if (!ok) throw TtsError(TTS_ERR_INVALID, std::string(op) + ": " + what);
+}
+
+void op_dtype(int dt, const char* op) {
+  op_require(dt == DT_F32 || dt == DT_F16 || dt == DT_BF16, op, "bad dtype");
+}
+
+std::string op_dims(std::initializer_list<std::pair<const char*, long long>> v) {
+  std::string s = " (";
+  for (const auto& p : v) s += std::string(s.size() > 2 ? ", " : "") + p.first + " " + std::to_string(p.second);
+  return s + ")";
+}
+
+constexpr int OP_MAX_GRID_YZ = 65535;
+
+template <typename F>
+int op_guard(F&& f) {
+  try {
+    f();
+    return TTS_OK;
+  } catch (const TtsError& e) {
+    g_last_error = e.what();
+    return e.code;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tts_op_embed(int dtype, const int32_t* ids, const int32_t* lens, int B, int N, int Tm, const void* table, int V,
+                 int D, float scale, void* out, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "embed");
+    op_require(ids && lens && table && out, "embed", "null buffer");
+    op_require(B > 0 && B <= OP_MAX_GRID_YZ && N > 0 && Tm > 0 && V > 0 && D > 0, "embed",
+               "needs 0 < B <= 65535 and N, Tm, V, D > 0" + op_dims({{"B", B}, {"N", N}, {"Tm", Tm}, {"V", V}, {"D", D}}));
+    HIP_CHECK(launch_embed(dtype, ids, lens, B, N, Tm, table, V, D, scale, out, (hipStream_t)stream));
+  });
+}
+
+int tts_op_layernorm(int dtype, const void* in, void* out, int rows, int C, const float* g1, const float* b1,
+                     const float* g2, const float* b2, float eps, const int32_t* lens, int stride, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "layernorm");
+    op_require(in && out && g1 && b1, "layernorm", "null buffer");
+    op_require((g2 != nullptr) == (b2 != nullptr), "layernorm", "g2 and b2 come together");
+    op_require(rows > 0 && C > 0, "layernorm", "needs rows, C > 0" + op_dims({{"rows", rows}, {"C", C}}));
+    op_require(C <= LN_MAX_C, "layernorm", "C " + std::to_string(C) + " above the kernels' " + std::to_string(LN_MAX_C) + " channels");
+    op_require(!lens || stride > 0, "layernorm", "lens needs a row stride > 0");
+    if (dtype != DT_F32 && C % 8 == 0)  // 16-byte row loads
+      op_require(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0, "layernorm",
+                 "16-bit rows of C % 8 == 0 channels must be 16-byte aligned");
+    HIP_CHECK(launch_layernorm(dtype, in, out, rows, C, g1, b1, g2, b2, eps, (hipStream_t)stream, lens, stride));
+  });
+}
+
+int tts_op_layernorm_groups(int dtype, void* x, int rows, int C, int ld, int groups, const float* const* g,
+                            const float* const* b, float eps, const int32_t* lens, int stride, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "layernorm_groups");
+    op_require(x && g && b, "layernorm_groups", "null buffer");
+    op_require(groups >= 1 && groups <= LnGroups::MAXG, "layernorm_groups",
+               "takes 1 to " + std::to_string(LnGroups::MAXG) + " groups, not " + std::to_string(groups));
+    op_require(rows > 0 && C > 0, "layernorm_groups", "needs rows, C > 0" + op_dims({{"rows", rows}, {"C", C}}));
+    op_require(C <= LN_PRED_MAX_C, "layernorm_groups",
+               "C " + std::to_string(C) + " above the kernel's " + std::to_string(LN_PRED_MAX_C) + " channels");
+    op_require(ld >= (long long)groups * C, "layernorm_groups", "ld " + std::to_string(ld) + " below groups * C");
+    op_require(!lens || stride > 0, "layernorm_groups", "lens needs a row stride > 0");
+    LnGroups gp{};
+    for (int i = 0; i < groups; ++i) {
+      op_require(g[i] && b[i], "layernorm_groups", "null gain or bias");
+      gp.g[i] = g[i];
+      gp.b[i] = b[i];
+    }
+    HIP_CHECK(launch_layernorm_groups(dtype, x, rows, C, ld, gp, groups, eps, (hipStream_t)stream, lens, stride));
+  });
+}
+
+int tts_op_pos_bias(int dtype, const void* qkv, int rows, int D, const float* u, const float* v, void* qu, void* qv,
+                    void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "pos_bias");
+    op_require(qkv && u && v && qu && qv, "pos_bias", "null buffer");
+    op_require(rows > 0 && D > 0, "pos_bias", "needs rows, D > 0" + op_dims({{"rows", rows}, {"D", D}}));
+    HIP_CHECK(launch_pos_bias(dtype, qkv, rows, D, u, v, qu, qv, (hipStream_t)stream));
+  });
+}
+
+int tts_op_transpose_v(int dtype, const void* qkv, const int32_t* lens, int B, int Tm, int D, int H, int Sk, void* vt,
+                       void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "transpose_v");
+    op_require(qkv && lens && vt, "transpose_v", "null buffer");
+    op_require(B > 0 && Tm > 0 && D > 0 && H > 0 && Sk > 0, "transpose_v",
+               "needs B, Tm, D, H, Sk > 0" + op_dims({{"B", B}, {"Tm", Tm}, {"D", D}, {"H", H}, {"Sk", Sk}}));
+    op_require(D % H == 0, "transpose_v", "D " + std::to_string(D) + " is not a multiple of H " + std::to_string(H));
+    op_require((long long)B * H <= OP_MAX_GRID_YZ, "transpose_v", "B * H above 65535");
+    if (dtype != DT_F32 && (D / H) % 64 == 0 && Sk % 8 == 0)  // transpose_v16_kernel: 16-byte loads and stores
+      op_require(((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(vt)) & 15) == 0, "transpose_v",
+                 "the 16-bit kernel needs 16-byte-aligned buffers");
+    HIP_CHECK(launch_transpose_v(dtype, qkv, lens, B, Tm, D, H, Sk, vt, (hipStream_t)stream));
+  });
+}
+
+int tts_op_rel_softmax(int dtype, const void* ac, const void* bd, const int32_t* lens, int B, int H, int Tm, int Sac,
+                       int Sbd, int Sk, float scale, void* p, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "rel_softmax");
+    op_require(ac && bd && lens && p, "rel_softmax", "null buffer");
+    op_require(B > 0 && H > 0 && Tm > 0, "rel_softmax", "needs B, H, Tm > 0" + op_dims({{"B", B}, {"H", H}, {"Tm", Tm}}));
+    op_require((long long)B * H <= OP_MAX_GRID_YZ, "rel_softmax", "B * H above 65535");
+    op_require(Sac >= Tm && Sk >= Tm && Sbd >= 2 * Tm - 1, "rel_softmax",
+               "needs Sac >= Tm, Sk >= Tm and Sbd >= 2 Tm - 1" + op_dims({{"Tm", Tm}, {"Sac", Sac}, {"Sbd", Sbd}, {"Sk", Sk}}));
+    HIP_CHECK(launch_rel_softmax(dtype, ac, bd, lens, B, H, Tm, Sac, Sbd, Sk, scale, p, (hipStream_t)stream));
+  });
+}
+
+int tts_op_glu_dwconv(int dtype, const void* a, const int32_t* lens, int B, int Tm, int D, const float* w, int k,
+                      const float* bias, void* out, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "glu_dwconv");
+    op_require(a && lens && w && bias && out, "glu_dwconv", "null buffer");
+    op_require(B > 0 && B <= OP_MAX_GRID_YZ && Tm > 0 && D > 0, "glu_dwconv",
+               "needs 0 < B <= 65535 and Tm, D > 0" + op_dims({{"B", B}, {"Tm", Tm}, {"D", D}}));
+    op_require(k >= 1 && k % 2 == 1 && k <= GLU_DWCONV_MAX_K, "glu_dwconv",
+               "kernel size " + std::to_string(k) + " is not odd and at most " + std::to_string(GLU_DWCONV_MAX_K));
+    const int epp = dtype == DT_F32 ? 4 : 8;
+    if ((k == 7 || k == 31) && D % epp == 0)  // glu_dwconv_k_kernel: 16-byte loads
+      op_require((reinterpret_cast<uintptr_t>(a) & 15) == 0, "glu_dwconv", "the k = 7 / 31 kernels need a 16-byte-aligned input");
+    HIP_CHECK(launch_glu_dwconv(dtype, a, lens, B, Tm, D, w, k, bias, out, (hipStream_t)stream));
+  });
+}
+
+int tts_op_durations(const float* logd, const int32_t* lens, int B, int N, const int32_t* override_d, float speed,
+                     int Tcap, int32_t* dur, int32_t* mel_lens, int32_t* tokmap, void* stream) {
+  return op_guard([&] {
+    op_require((logd || override_d) && lens && dur && mel_lens && tokmap, "durations", "null buffer");
+    op_require(B > 0 && N > 0 && Tcap > 0, "durations", "needs B, N, Tcap > 0" + op_dims({{"B", B}, {"N", N}, {"Tcap", Tcap}}));
+    op_require(((long long)N + 1) * (long long)sizeof(int) <= 64 * 1024, "durations",
+               "N " + std::to_string(N) + " tokens do not fit the kernel's 64 KiB prefix-sum tile");
+    op_require(speed > 0.f && std::isfinite(speed), "durations", "speed must be positive and finite");
+    HIP_CHECK(launch_durations(logd, lens, B, N, override_d, speed, Tcap, dur, mel_lens, tokmap, (hipStream_t)stream));
+  });
+}
+
+int tts_op_var_embed_add(int dtype, void* x, int rows, int D, const float* e, const float* we, const float* be,
+                         const float* p, const float* wp, const float* bp, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "var_embed_add");
+    op_require(x && e && we && be && p && wp && bp, "var_embed_add", "null buffer");
+    op_require(rows > 0 && D > 0, "var_embed_add", "needs rows, D > 0" + op_dims({{"rows", rows}, {"D", D}}));
+    HIP_CHECK(launch_var_embed_add(dtype, x, rows, D, e, we, be, p, wp, bp, (hipStream_t)stream));
+  });
+}
+
+int tts_op_regulate(int dtype_in, int dtype, const void* enc, int B, int N, int D, const int32_t* tokmap, int Tcap,
+                    int frames, int Tout, float scale, void* out, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "regulate");
+    op_dtype(dtype_in, "regulate");
+    op_require(dtype_in == dtype || dtype_in == DT_F32, "regulate", "the input is of the output's dtype or fp32");
+    op_require(enc && tokmap && out, "regulate", "null buffer");
+    op_require(B > 0 && B <= OP_MAX_GRID_YZ && N > 0 && D > 0 && Tcap > 0 && Tout > 0 && frames > 0, "regulate",
+               "needs 0 < B <= 65535 and N, D, Tcap, Tout, frames > 0" +
+                   op_dims({{"B", B}, {"N", N}, {"D", D}, {"Tcap", Tcap}, {"Tout", Tout}, {"frames", frames}}));
+    op_require(frames <= Tcap && frames <= Tout, "regulate",
+               "frames " + std::to_string(frames) + " above Tcap " + std::to_string(Tcap) + " or Tout " + std::to_string(Tout));
+    HIP_CHECK(launch_regulate(dtype_in, dtype, enc, B, N, D, tokmap, Tcap, frames, Tout, scale, out, (hipStream_t)stream));
+  });
+}
+
+int tts_op_mel_out(int dtype, const void* in, const int32_t* mel_lens, int B, int Tin, int Tcap, int C, float* out,
+                   void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "mel_out");
+    op_require(in && mel_lens && out, "mel_out", "null buffer");
+    op_require(B > 0 && B <= OP_MAX_GRID_YZ && Tin > 0 && Tcap > 0 && C > 0, "mel_out",
+               "needs 0 < B <= 65535 and Tin, Tcap, C > 0" + op_dims({{"B", B}, {"Tin", Tin}, {"Tcap", Tcap}, {"C", C}}));
+    HIP_CHECK(launch_mel_out(dtype, in, mel_lens, B, Tin, Tcap, C, out, (hipStream_t)stream));
+  });
+}
+
+int tts_op_spk_bias(int dtype, const float* e, int B, int E, const float* We, const float* bias, int D, void* out,
+                    void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "spk_bias");
+    op_require(e && We && bias && out, "spk_bias", "null buffer");
+    op_require(B > 0 && E > 0 && D > 0, "spk_bias", "needs B, E, D > 0" + op_dims({{"B", B}, {"E", E}, {"D", D}}));
+    HIP_CHECK(launch_spk_bias(dtype, e, B, E, We, bias, D, out, (hipStream_t)stream));
+  });
+}
+
 }  // extern "C"

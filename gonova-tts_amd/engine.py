@@ -113,6 +113,18 @@ C_API = [
     ("tts_op_conv_layer_destroy", None, [_VP]),
     ("tts_op_conv1d_ex", _I, [_VP, ctypes.POINTER(TtsConvDesc), ctypes.POINTER(TtsConvExt), _VP]),
     ("tts_op_conv_ws_bytes", ctypes.c_int64, [_I, _I, _I, _I]),
+    ("tts_op_embed", _I, [_I, _VP, _VP, _I, _I, _I, _VP, _I, _I, _F, _VP, _VP]),
+    ("tts_op_layernorm", _I, [_I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _F, _VP, _I, _VP]),
+    ("tts_op_layernorm_groups", _I, [_I, _VP, _I, _I, _I, _I, ctypes.POINTER(_VP), ctypes.POINTER(_VP), _F, _VP, _I, _VP]),
+    ("tts_op_pos_bias", _I, [_I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    ("tts_op_transpose_v", _I, [_I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
+    ("tts_op_rel_softmax", _I, [_I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _F, _VP, _VP]),
+    ("tts_op_glu_dwconv", _I, [_I, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP]),
+    ("tts_op_durations", _I, [_VP, _VP, _I, _I, _VP, _F, _I, _VP, _VP, _VP, _VP]),
+    ("tts_op_var_embed_add", _I, [_I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("tts_op_regulate", _I, [_I, _I, _VP, _I, _I, _I, _VP, _I, _I, _I, _F, _VP, _VP]),
+    ("tts_op_mel_out", _I, [_I, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    ("tts_op_spk_bias", _I, [_I, _VP, _I, _I, _VP, _VP, _I, _VP, _VP]),
 ]
 
 _lib = None
@@ -578,3 +590,73 @@ def rel_attn_op(dtype: str, pos_u, pos_v, qkv, ptab, lens, Tm: int, rmax: int, s
                               D3 // 3, H, rmax, float(scale), vp(out), vp(range_flag), vp(ws),
                               ws.numel() * ws.element_size() if ws is not None else 0, _stream_ptr(stream)),
           "tts_op_rel_attn")
+
+
+# ---- op-level entries of the acoustic model's row-wise kernels (include/tts_hip.h states each
+# contract).  Thin: buffers are torch device tensors (or None / a raw address), extents are given as
+# the launchers take them, nothing is allocated or copied here.
+def _p(t):
+    return ctypes.c_void_p(0 if t is None else t if isinstance(t, int) else t.data_ptr())
+
+
+def embed_op(dtype, ids, lens, B, N, Tm, table, V, D, scale, out, stream=None):
+    check(load_library().tts_op_embed(DTYPES[dtype], _p(ids), _p(lens), B, N, Tm, _p(table), V, D, float(scale), _p(out),
+                                      _stream_ptr(stream)), "tts_op_embed")
+
+
+def layernorm_op(dtype, x, out, rows, C, g1, b1, g2=None, b2=None, eps=1e-5, lens=None, stride=0, stream=None):
+    check(load_library().tts_op_layernorm(DTYPES[dtype], _p(x), _p(out), rows, C, _p(g1), _p(b1), _p(g2), _p(b2), float(eps),
+                                          _p(lens), stride, _stream_ptr(stream)), "tts_op_layernorm")
+
+
+def layernorm_groups_op(dtype, x, rows, C, ld, gains, biases, eps=1e-5, lens=None, stride=0, stream=None):
+    """gains / biases: one fp32 device tensor per group."""
+    n = len(gains)
+    arr = lambda ts: (ctypes.c_void_p * max(n, 1))(*[_p(t).value or 0 for t in ts])
+    check(load_library().tts_op_layernorm_groups(DTYPES[dtype], _p(x), rows, C, ld, n, arr(gains), arr(biases), float(eps),
+                                                 _p(lens), stride, _stream_ptr(stream)), "tts_op_layernorm_groups")
+
+
+def pos_bias_op(dtype, qkv, rows, D, u, v, qu, qv, stream=None):
+    check(load_library().tts_op_pos_bias(DTYPES[dtype], _p(qkv), rows, D, _p(u), _p(v), _p(qu), _p(qv), _stream_ptr(stream)),
+          "tts_op_pos_bias")
+
+
+def transpose_v_op(dtype, qkv, lens, B, Tm, D, H, Sk, vt, stream=None):
+    check(load_library().tts_op_transpose_v(DTYPES[dtype], _p(qkv), _p(lens), B, Tm, D, H, Sk, _p(vt), _stream_ptr(stream)),
+          "tts_op_transpose_v")
+
+
+def rel_softmax_op(dtype, ac, bd, lens, B, H, Tm, Sac, Sbd, Sk, scale, p, stream=None):
+    check(load_library().tts_op_rel_softmax(DTYPES[dtype], _p(ac), _p(bd), _p(lens), B, H, Tm, Sac, Sbd, Sk, float(scale),
+                                            _p(p), _stream_ptr(stream)), "tts_op_rel_softmax")
+
+
+def glu_dwconv_op(dtype, a, lens, B, Tm, D, w, k, bias, out, stream=None):
+    check(load_library().tts_op_glu_dwconv(DTYPES[dtype], _p(a), _p(lens), B, Tm, D, _p(w), k, _p(bias), _p(out),
+                                           _stream_ptr(stream)), "tts_op_glu_dwconv")
+
+
+def durations_op(logd, lens, B, N, Tcap, dur, mel_lens, tokmap, override_d=None, speed=1.0, stream=None):
+    check(load_library().tts_op_durations(_p(logd), _p(lens), B, N, _p(override_d), float(speed), Tcap, _p(dur), _p(mel_lens),
+                                          _p(tokmap), _stream_ptr(stream)), "tts_op_durations")
+
+
+def var_embed_add_op(dtype, x, rows, D, e, we, be, p, wp, bp, stream=None):
+    check(load_library().tts_op_var_embed_add(DTYPES[dtype], _p(x), rows, D, _p(e), _p(we), _p(be), _p(p), _p(wp), _p(bp),
+                                              _stream_ptr(stream)), "tts_op_var_embed_add")
+
+
+def regulate_op(dtype_in, dtype, enc, B, N, D, tokmap, Tcap, frames, Tout, scale, out, stream=None):
+    check(load_library().tts_op_regulate(DTYPES[dtype_in], DTYPES[dtype], _p(enc), B, N, D, _p(tokmap), Tcap, frames, Tout,
+                                         float(scale), _p(out), _stream_ptr(stream)), "tts_op_regulate")
+
+
+def mel_out_op(dtype, x, mel_lens, B, Tin, Tcap, C, out, stream=None):
+    check(load_library().tts_op_mel_out(DTYPES[dtype], _p(x), _p(mel_lens), B, Tin, Tcap, C, _p(out), _stream_ptr(stream)),
+          "tts_op_mel_out")
+
+
+def spk_bias_op(dtype, e, B, E, We, bias, D, out, stream=None):
+    check(load_library().tts_op_spk_bias(DTYPES[dtype], _p(e), B, E, _p(We), _p(bias), D, _p(out), _stream_ptr(stream)),
+          "tts_op_spk_bias")

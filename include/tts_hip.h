@@ -387,6 +387,94 @@ int tts_op_rel_attn(int dtype, int split, const float* pos_u, const float* pos_v
  * TTS_ATTN_F32_KC (0: none, one chunk covers Tm). */
 int64_t tts_op_rel_attn_ws_bytes(int B, int Tm, int Tp, int D, int H);
 
+/* ---- op-level entries of the acoustic model's row-wise kernels (one launch each) ----
+ * (ABI 5, additive; a caller detects them by symbol.)  Every pointer is a device pointer, dtype a
+ * TTS_DTYPE_* (the type of every `void*` activation; gains, biases, tables of weights named float
+ * are fp32), every buffer dense in the layout given, lens[b] int32.  Null buffers, extents <= 0
+ * and whatever else an entry names are TTS_ERR_INVALID with a message, nothing launched.
+ * For all of them: input rows that the entry says are masked never reach a valid output, whatever
+ * they hold (NaN and inf included), and a valid row's bits depend on its own utterance only -- not
+ * on B, on the other utterances or on what lies past its length.
+ *
+ * embed: out[b][t][:] = round(fp32(table[clamp(ids[b][t], 0, V - 1)][:]) * scale) for t < len,
+ *   len = min(lens[b], N): one fp32 multiply, one rounding.  ids [B][N] int32, table [V][D],
+ *   out [B][Tm][D].  Rows t in [len, Tm) are written as zeros (Tm < len: only Tm rows exist);
+ *   ids at or past len are not read. */
+int tts_op_embed(int dtype, const int32_t* ids, const int32_t* lens, int B, int N, int Tm, const void* table, int V,
+                 int D, float scale, void* out, void* stream);
+/* layernorm: out[r] = LN2?(LN1(in[r])) over C <= 512 channels (more: refused), rows [rows][C];
+ *   fp32 two-pass mean / variance (biased, eps inside the root), LN1's result rounded to dtype
+ *   before LN2 (g2 / b2 NULL: one LayerNorm).  lens (optional, with stride > 0): row r belongs to
+ *   utterance r / stride and is skipped -- neither read nor written -- when r % stride >= lens[b].
+ *   in == out is fine.  The gains need 4-byte alignment only: 16-byte-aligned ones load as
+ *   vectors in the 16-bit C % 8 == 0 kernel, to the same bits.
+ * layernorm_groups: `groups` (1..4) LayerNorms of C <= 256 channels side by side, in place, in rows
+ *   of ld >= groups * C elements: channels [i C, (i + 1) C) with g[i] / b[i] (host arrays of device
+ *   pointers).  Columns at or past groups * C and rows masked by lens are left alone. */
+int tts_op_layernorm(int dtype, const void* in, void* out, int rows, int C, const float* g1, const float* b1,
+                     const float* g2, const float* b2, float eps, const int32_t* lens, int stride, void* stream);
+int tts_op_layernorm_groups(int dtype, void* x, int rows, int C, int ld, int groups, const float* const* g,
+                            const float* const* b, float eps, const int32_t* lens, int stride, void* stream);
+/* pos_bias: qu[r][c] = round(fp32(q[r][c]) + u[c]), qv likewise with v: q the first D of the 3 D
+ *   columns of qkv row r; qu / qv [rows][D]; u / v fp32 [D].  Every row is read and written (no
+ *   lengths: a row stays private to itself). */
+int tts_op_pos_bias(int dtype, const void* qkv, int rows, int D, const float* u, const float* v, void* qu, void* qv,
+                    void* stream);
+/* transpose_v: vt[b][h][d][j] = v[b][j][h dk + d], v the last D columns of qkv [B][Tm][3 D],
+ *   dk = D / H (D % H != 0: refused), vt [B][H][dk][Sk].  Bits are copied (-0, subnormals, inf).
+ *   With len = min(lens[b], Tm): keys j in [len, Sk) are written as zeros whatever qkv holds there
+ *   (those rows are not read); keys j >= Sk are dropped; nothing is written at or past Sk. */
+int tts_op_transpose_v(int dtype, const void* qkv, const int32_t* lens, int B, int Tm, int D, int H, int Sk, void* vt,
+                       void* stream);
+/* rel_softmax: p[b,h][i][j] = softmax_j((ac[b,h][i][j] + bd[b,h][i][Tm - 1 - i + j]) * scale) over
+ *   j < len = min(lens[b], Tm); ac [B H][Tm][Sac], bd [B H][Tm][Sbd], p [B H][Tm][Sk] with Sac, Sk
+ *   >= Tm and Sbd >= 2 Tm - 1 (else refused).  The maximum is subtracted before the exponential.
+ *   Columns j in [len, Sk) of every row are written as zeros; columns >= len of ac and
+ *   >= Tm - 1 - i + len of bd row i are not read.  Rows i in [len, Tm) ARE computed, from whatever
+ *   ac / bd hold there over the same len keys: a caller masks them downstream (the model's P.V GEMM
+ *   does).  An utterance of length 0 is treated as length 1: column 0 of every row is read and
+ *   written (1, or NaN when the inputs there are not finite), the rest zeros. */
+int tts_op_rel_softmax(int dtype, const void* ac, const void* bd, const int32_t* lens, int B, int H, int Tm, int Sac,
+                       int Sbd, int Sk, float scale, void* p, void* stream);
+/* glu_dwconv: g[t][c] = a[t][c] * sigmoid(a[t][D + c]); out[t][c] = SiLU(bias[c] + sum_j w[c][j] *
+ *   g[t + j - (k - 1) / 2][c]), g outside [0, len) taken as 0, len = min(lens[b], Tm); a [B][Tm][2 D],
+ *   out [B][Tm][D], w fp32 [D][k], k odd and <= 129 (else refused).  Rows t >= len of out are never
+ *   written and rows >= len of a never read; an utterance of length 0 writes nothing. */
+int tts_op_glu_dwconv(int dtype, const void* a, const int32_t* lens, int B, int Tm, int D, const float* w, int k,
+                      const float* bias, void* out, void* stream);
+/* durations: per utterance, len = min(lens[b], N) (N <= 16383):
+ *     d[t] = max(override_d[b][t], 0) when override_d is given, else max(rint(expf(logd[b][t]) - 1), 0),
+ *     then rint(d * speed) when speed != 1 (ties to even both times); t >= len: d = 0, logd /
+ *     override_d there are not read; if every d is 0 and len > 0, d[t] = 1 for t < len.
+ *   dur [B][N]       d, all N entries written, NOT clamped to Tcap
+ *   mel_lens [b]     min(sum d, Tcap)
+ *   tokmap [B][Tcap] frame f < mel_lens[b]: the token t with sum_{s<t} d[s] <= f < sum_{s<=t} d[s]
+ *                    (never one of duration 0); f >= mel_lens[b]: -1.  With sum d > Tcap the map
+ *                    holds the first Tcap frames, and sum(dur) > mel_lens tells the caller. */
+int tts_op_durations(const float* logd, const int32_t* lens, int B, int N, const int32_t* override_d, float speed,
+                     int Tcap, int32_t* dur, int32_t* mel_lens, int32_t* tokmap, void* stream);
+/* var_embed_add, in place on x [rows][D]: x = round(round(x + round(e[r] we[c] + be[c])) +
+ *   round(p[r] wp[c] + bp[c])), every round to dtype (HF adds the two embeddings one after the
+ *   other in the model's dtype); e / p fp32 [rows], we / be / wp / bp fp32 [D].  Every row is
+ *   read and written. */
+int tts_op_var_embed_add(int dtype, void* x, int rows, int D, const float* e, const float* we, const float* be,
+                         const float* p, const float* wp, const float* bp, void* stream);
+/* regulate: out[b][f][:] = round(fp32(enc[b][tokmap[b][f]][:]) * scale) for f < frames; enc [B][N][D]
+ *   of dtype_in (dtype, or fp32 with a 16-bit dtype; another pair is refused), tokmap [B][Tcap] with
+ *   entries < N, out [B][Tout][D], frames <= Tcap and <= Tout (else refused).  A frame whose token
+ *   is negative is written as zeros; rows f in [frames, Tout) are never written. */
+int tts_op_regulate(int dtype_in, int dtype, const void* enc, int B, int N, int D, const int32_t* tokmap, int Tcap,
+                    int frames, int Tout, float scale, void* out, void* stream);
+/* mel_out: out[b][t][:] = fp32(in[b][t][:]) for t < min(mel_lens[b], Tcap), zeros for the other rows
+ *   below Tcap; in [B][Tin][C] with mel_lens[b] <= Tin (rows at or past it are not read), out fp32
+ *   [B][Tcap][C].  Bits are copied (widened). */
+int tts_op_mel_out(int dtype, const void* in, const int32_t* mel_lens, int B, int Tin, int Tcap, int C, float* out,
+                   void* stream);
+/* spk_bias: out[b][o] = round(bias[o] + (sum_i We[o][i] e[b][i]) / max(||e[b]||, 1e-12)); e fp32
+ *   [B][E], We fp32 [D][E], bias fp32 [D], out [B][D].  The norm runs over all E elements. */
+int tts_op_spk_bias(int dtype, const float* e, int B, int E, const float* We, const float* bias, int D, void* out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
