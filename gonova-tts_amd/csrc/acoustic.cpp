@@ -832,7 +832,7 @@ struct AcousticModel::Impl {
   }
 
   void forward(const int* tokens, const int* tok_lens, int B, int N, const int* dur_override, float* mel,
-               int* mel_lens, int Tcap, int* durations, const float* spk, hipStream_t s) {
+               int* mel_lens, int Tcap, int* durations, const float* spk, hipStream_t s, const VarianceCtl* ctl) {
     reserve(B, N, Tcap);
     const int Tm = std::max(N, Tcap);
     {  // the unfused attention's score buffers, for the stacks that run it (fp32 / TTS_REL_ATTN=0)
@@ -876,8 +876,17 @@ struct AcousticModel::Impl {
     cur_rpad = 0;
     // logd is laid out [B][Np]; durations kernel reads [B][N] rows -> compact view via stride Np
     int* dur = durations ? durations : i_dur;
-    elem(s, [&] { return launch_durations_strided(s, B, N, Np, tok_lens, dur_override, Tcap, dur, mel_lens); });
-    elem(s, [&] { return launch_var_embed_add(dte, ENC, B * Np, D, f_energy, ee_w, ee_b, f_pitch, pe_w, pe_b, s); });
+    if (ctl) {
+      // per-utterance prosody controls: durations (logd read at its row stride), the pitch / energy
+      // controls and the embedding add in one launch
+      elem(s, [&] {
+        return launch_variance_adapt(dte, ENC, f_logd, f_pitch, f_energy, tok_lens, dur_override, *ctl, B, N, Np, D,
+                                     Tcap, ee_w, ee_b, pe_w, pe_b, dur, mel_lens, i_tokmap, s);
+      });
+    } else {
+      elem(s, [&] { return launch_durations_strided(s, B, N, Np, tok_lens, dur_override, Tcap, dur, mel_lens); });
+      elem(s, [&] { return launch_var_embed_add(dte, ENC, B * Np, D, f_energy, ee_w, ee_b, f_pitch, pe_w, pe_b, s); });
+    }
     // Decoder extent.  With predicted durations the caller's Tcap is a frame budget (model.py: 12
     // frames per token, retried exactly if exceeded), typically twice the frames the durations
     // give; the decoder then runs at the longest utterance's frame count, read back here (one
@@ -1030,9 +1039,9 @@ void AcousticModel::reserve(int B, int N, int T) {
 
 void AcousticModel::forward(const int32_t* tokens, const int32_t* tok_lens, int B, int N, const int32_t* dur_override,
                             float* mel, int32_t* mel_lens, int Tcap, int32_t* durations, const float* spk,
-                            hipStream_t s) {
+                            hipStream_t s, const VarianceCtl* ctl) {
   if (!impl) throw TtsError(TTS_ERR_STATE, "acoustic model not loaded");
-  impl->forward(tokens, tok_lens, B, N, dur_override, mel, mel_lens, Tcap, durations, spk, s);
+  impl->forward(tokens, tok_lens, B, N, dur_override, mel, mel_lens, Tcap, durations, spk, s, ctl);
 }
 
 int AcousticModel::speaker_dim() const { return impl ? impl->E : 0; }

@@ -10,6 +10,7 @@
 namespace tts {
 
 struct Profiler;
+struct VarianceCtl;  // acoustic_kernels.h: per-utterance prosody controls (device arrays)
 
 struct AcousticModel {
   bool loaded = false;
@@ -23,8 +24,11 @@ struct AcousticModel {
                 bool f32_split_enc = false);
   void reserve(int B, int N, int T);
   // spk: optional [B][speaker_dim()] fp32 speaker embeddings (ignored when the model has none)
+  // ctl: optional prosody controls; given, the variance adaptor runs as the one fused launch
+  // (variance_adapt_ctl_kernel), null: the plain launches
   void forward(const int32_t* tokens, const int32_t* tok_lens, int B, int N, const int32_t* dur_override,
-               float* mel, int32_t* mel_lens, int Tcap, int32_t* durations, const float* spk, hipStream_t s);
+               float* mel, int32_t* mel_lens, int Tcap, int32_t* durations, const float* spk, hipStream_t s,
+               const VarianceCtl* ctl = nullptr);
   int speaker_dim() const;
   // encoder side on split-precision GEMMs and attention (a 16-bit model's exact encoder, or an
   // fp32 model's with f32_split_enc)

@@ -39,6 +39,20 @@ hipError_t launch_durations(const float* logd, const int* lens, int B, int N, co
                             int Tcap, int* dur, int* mel_lens, int* tokmap, hipStream_t s);
 hipError_t launch_var_embed_add(int dt, void* x, int rows, int D, const float* e, const float* we, const float* be,
                                 const float* p, const float* wp, const float* bp, hipStream_t s);
+// per-utterance prosody controls, device fp32 [B] each; a null array is neutral for every utterance
+struct VarianceCtl {
+  const float* duration_scale = nullptr;
+  const float* pitch_shift = nullptr;
+  const float* pitch_range = nullptr;
+  const float* energy_shift = nullptr;
+  const float* energy_range = nullptr;
+};
+// variance_adapt_ctl_kernel: durations (logd / pitch / energy rows of stride Np, override_d [B][N]),
+// the pitch / energy controls in place and the embedding add on x [B][Np][D], one launch; N <= 16383
+hipError_t launch_variance_adapt(int dt, void* x, const float* logd, float* pitch, float* energy, const int* lens,
+                                 const int* override_d, const VarianceCtl& ctl, int B, int N, int Np, int D, int Tcap,
+                                 const float* we, const float* be, const float* wp, const float* bp, int* dur,
+                                 int* mel_lens, int* tokmap, hipStream_t s);
 // enc in dt_in (dt or fp32), out in dt: frames <= Tcap rows per utterance (tokmap row stride Tcap)
 // written at row stride Tout
 hipError_t launch_regulate(int dt_in, int dt, const void* enc, int B, int N, int D, const int* tokmap, int Tcap,

@@ -4,6 +4,7 @@
 //
 // Activations: [B][Tm][C] channels-last in the compute dtype T; per-utterance valid
 // lengths `lens[b]` give B=1 semantics (rows >= len are never read by valid rows).
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 
@@ -392,6 +393,73 @@ __global__ __launch_bounds__(256) void ln_linear1_kernel(const T* __restrict__ i
 // HF:104-109, per utterance), exclusive prefix sums, mel lengths (clamped to Tcap) and the
 // frame -> token map.  One block per utterance.
 // ---------------------------------------------------------------------------
+// The pieces below are shared by durations_kernel / var_embed_add_kernel and by
+// variance_adapt_ctl_kernel, so the controlled forward's bits cannot drift from the plain one's.
+
+// a length_regulator speed the kernels apply: positive and finite, else 1 (no scaling)
+__device__ inline float dur_speed(float speed) { return speed > 0.f && speed <= 3.402823466e38f ? speed : 1.0f; }
+
+// one token's frame count: the override (negative -> 0) or the prediction, then the speed
+__device__ inline int dur_token(const float* __restrict__ logd, const int* __restrict__ override_d, long long il,
+                                long long io, float speed) {
+  int d;
+  if (override_d) {
+    d = max(override_d[io], 0);
+  } else {
+    const float x = logd[il];
+    d = (int)fmaxf(rintf(expf(x) - 1.0f), 0.f);  // rint = round half to even, like torch.round
+  }
+  if (speed != 1.0f) d = (int)rintf((float)d * speed);
+  return d;
+}
+
+// one thread: cum[1..N] hold the frame counts on entry, the cumulative counts on return
+// (cum[0] = 0); the all-zero rule gives every token of the utterance one frame.  -> cum[N]
+__device__ inline int dur_prefix(int* cum, int N, int L) {
+  cum[0] = 0;
+  int s = 0;
+  for (int t = 1; t <= N; ++t) s += cum[t];
+  if (s == 0 && L > 0) {  // all-zero rule: every token gets one frame
+    for (int t = 1; t <= N; ++t) cum[t] = (t <= L) ? 1 : 0;
+  }
+  for (int t = 1; t <= N; ++t) cum[t] += cum[t - 1];  // inclusive -> cumulative
+  return cum[N];
+}
+
+// the token of frame f < cum[N]: first t with cum[t+1] > f
+__device__ inline int dur_token_of(const int* cum, int N, int f) {
+  int lo = 0, hi = N - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cum[mid + 1] > f) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// One embedding term, v * w + b as one fused multiply-add, rounded to T.  Spelled out so that
+// every caller gets var_embed_add_kernel's bits whatever the loop around it compiles to: left as
+// `v * w + b`, f16 callers got v_fma_mixlo_f16 (the exact fma rounded once to f16) in a scalar loop
+// body and an fp32 fma with a second rounding in a body unrolled by two.
+template <typename T>
+__device__ inline float var_embed_term(float v, float w, float b) {
+  return to_f32(from_f32<T>(fmaf(v, w, b)));
+}
+template <>
+__device__ inline float var_embed_term<half_t>(float v, float w, float b) {
+  unsigned r;  // the low half holds the result (fp32 sources, one rounding); the high half is not read
+  asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(w), "v"(b));
+  return to_f32(__builtin_bit_cast(half_t, (unsigned short)r));
+}
+
+// (x + (e * we + be)) + (p * wp + bp), every step rounded to T    (HF:1216-1218)
+template <typename T>
+__device__ inline T var_embed_chain(T x, float e, float we, float be, float p, float wp, float bp) {
+  const float ee = var_embed_term<T>(e, we, be);
+  const float pp = var_embed_term<T>(p, wp, bp);
+  const float y = to_f32(from_f32<T>(to_f32(x) + ee));
+  return from_f32<T>(y + pp);
+}
+
 __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict__ logd, const int* __restrict__ lens,
                                                        int N, const int* __restrict__ override_d, float speed,
                                                        int Tcap, int* __restrict__ dur, int* __restrict__ mel_lens,
@@ -401,46 +469,18 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict_
   const int b = blockIdx.x;
   const int L = min(lens[b], N);
   int* cum = sm;
-  for (int t = threadIdx.x; t < N; t += blockDim.x) {
-    int d = 0;
-    if (t < L) {
-      if (override_d) {
-        d = max(override_d[(long long)b * N + t], 0);
-      } else {
-        const float x = logd[(long long)b * N + t];
-        d = (int)fmaxf(rintf(expf(x) - 1.0f), 0.f);  // rint = round half to even, like torch.round
-      }
-      if (speed != 1.0f) d = (int)rintf((float)d * speed);
-    }
-    cum[t + 1] = d;
-  }
+  for (int t = threadIdx.x; t < N; t += blockDim.x)
+    cum[t + 1] = t < L ? dur_token(logd, override_d, (long long)b * N + t, (long long)b * N + t, speed) : 0;
   __syncthreads();
   if (threadIdx.x == 0) {
-    cum[0] = 0;
-    int s = 0;
-    for (int t = 1; t <= N; ++t) s += cum[t];
-    if (s == 0 && L > 0) {  // all-zero rule: every token gets one frame
-      for (int t = 1; t <= N; ++t) cum[t] = (t <= L) ? 1 : 0;
-    }
-    for (int t = 1; t <= N; ++t) cum[t] += cum[t - 1];  // inclusive -> cumulative
-    total = min(cum[N], Tcap);
+    total = min(dur_prefix(cum, N, L), Tcap);
     mel_lens[b] = total;
   }
   __syncthreads();
   for (int t = threadIdx.x; t < N; t += blockDim.x) dur[(long long)b * N + t] = cum[t + 1] - cum[t];
   const int tot = total;
-  for (int f = threadIdx.x; f < Tcap; f += blockDim.x) {
-    int tok = -1;
-    if (f < tot) {
-      int lo = 0, hi = N - 1;  // first t with cum[t+1] > f
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cum[mid + 1] > f) hi = mid; else lo = mid + 1;
-      }
-      tok = lo;
-    }
-    tokmap[(long long)b * Tcap + f] = tok;
-  }
+  for (int f = threadIdx.x; f < Tcap; f += blockDim.x)
+    tokmap[(long long)b * Tcap + f] = f < tot ? dur_token_of(cum, N, f) : -1;
 }
 
 // x[row][c] = (x + (e[row] * we[c] + be[c])) + (p[row] * wp[c] + bp[c])    (HF:1216-1218)
@@ -453,10 +493,110 @@ __global__ void var_embed_add_kernel(T* __restrict__ x, int rows, int D, const f
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const long long r = i / D;
     const int c = (int)(i - r * D);
-    const float ee = to_f32(from_f32<T>(e[r] * we[c] + be[c]));
-    const float pp = to_f32(from_f32<T>(p[r] * wp[c] + bp[c]));
-    const float y = to_f32(from_f32<T>(to_f32(x[i]) + ee));
-    x[i] = from_f32<T>(y + pp);
+    x[i] = var_embed_chain<T>(x[i], e[r], we[c], be[c], p[r], wp[c], bp[c]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The variance adaptor of a forward with per-utterance prosody controls, one launch in place of
+// the logd compaction, durations_kernel and var_embed_add_kernel.  One block per utterance b
+// (len = min(lens[b], N) valid tokens; logd / pitch / energy rows of stride Np, x [B][Np][D]):
+//   durations   as durations_kernel with speed = duration_scale[b] (not positive or not finite: 1)
+//   pitch       p'[t] = m + pitch_range[b] (p[t] - m) + pitch_shift[b] for t < len, written in place,
+//               m the fp32 mean of p over the len valid tokens; range 1 and shift 0: p is left as it is
+//   energy      the same with its own two controls
+//   x           valid rows get var_embed_add_kernel's chain with p' and e'
+// A null control array is neutral for every utterance.  Tokens at or past len are neither read
+// into a sum nor written.  The mean is summed in an order len alone fixes: thread i adds tokens
+// i, i + 1024, ... in increasing t, then the xor butterfly of its wave, then the 16 wave sums
+// pairwise ((w0 + w1) + (w2 + w3)) + ...; nothing depends on B or on another utterance.
+// ---------------------------------------------------------------------------
+constexpr int VA_THREADS = 1024;
+constexpr size_t VA_LDS_MIN = 2 * (VA_THREADS / 64) * sizeof(float);
+
+// both means at once; every thread returns the same pair.  red: 2 * VA_THREADS / 64 floats of LDS,
+// free for other use on return
+__device__ inline void va_means(const float* __restrict__ p, const float* __restrict__ e, int L, float* red, float& mp,
+                                float& me) {
+  constexpr int W = VA_THREADS / 64;
+  float sp = 0.f, se = 0.f;
+  for (int t = threadIdx.x; t < L; t += VA_THREADS) {
+    sp += p[t];
+    se += e[t];
+  }
+  sp = wave_sum(sp);
+  se = wave_sum(se);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = sp;
+    red[W + (threadIdx.x >> 6)] = se;
+  }
+  __syncthreads();
+  float vp[W], ve[W];
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    vp[i] = red[i];
+    ve[i] = red[W + i];
+  }
+#pragma unroll
+  for (int n = W; n > 1; n >>= 1) {
+#pragma unroll
+    for (int i = 0; i < n / 2; ++i) {
+      vp[i] = vp[2 * i] + vp[2 * i + 1];
+      ve[i] = ve[2 * i] + ve[2 * i + 1];
+    }
+  }
+  mp = vp[0] / (float)L;
+  me = ve[0] / (float)L;
+  __syncthreads();
+}
+
+template <typename T>
+__global__ __launch_bounds__(VA_THREADS) void variance_adapt_ctl_kernel(
+    T* __restrict__ x, const float* __restrict__ logd, float* __restrict__ pitch, float* __restrict__ energy,
+    const int* __restrict__ lens, const int* __restrict__ override_d, const float* __restrict__ c_scale,
+    const float* __restrict__ c_pshift, const float* __restrict__ c_prange, const float* __restrict__ c_eshift,
+    const float* __restrict__ c_erange, int N, int Np, int D, int Tcap, const float* __restrict__ we,
+    const float* __restrict__ be, const float* __restrict__ wp, const float* __restrict__ bp, int* __restrict__ dur,
+    int* __restrict__ mel_lens, int* __restrict__ tokmap) {
+  // cum[N + 1], and before that the means' wave sums (VA_LDS_MIN bytes at least); no static LDS,
+  // so N = 16383 still fits the 64 KiB a launch gets
+  extern __shared__ int sm[];
+  const int b = blockIdx.x;
+  const int L = min(lens[b], N);
+  int* cum = sm;
+  float* p = pitch + (long long)b * Np;
+  float* e = energy + (long long)b * Np;
+  const float pr = c_prange ? c_prange[b] : 1.0f, ps = c_pshift ? c_pshift[b] : 0.f;
+  const float er = c_erange ? c_erange[b] : 1.0f, es = c_eshift ? c_eshift[b] : 0.f;
+  const bool on_p = !(pr == 1.0f && ps == 0.f), on_e = !(er == 1.0f && es == 0.f);
+  float mp = 0.f, me = 0.f;
+  if (L > 0 && (on_p || on_e)) va_means(p, e, L, reinterpret_cast<float*>(sm), mp, me);  // (block-uniform)
+  // durations, prefix sums, frame count and the frame -> token map
+  const float speed = dur_speed(c_scale ? c_scale[b] : 1.0f);
+  for (int t = threadIdx.x; t < N; t += VA_THREADS)
+    cum[t + 1] = t < L ? dur_token(logd, override_d, (long long)b * Np + t, (long long)b * N + t, speed) : 0;
+  __syncthreads();
+  if (threadIdx.x == 0) mel_lens[b] = min(dur_prefix(cum, N, L), Tcap);
+  __syncthreads();
+  for (int t = threadIdx.x; t < N; t += VA_THREADS) dur[(long long)b * N + t] = cum[t + 1] - cum[t];
+  const int tot = min(cum[N], Tcap);
+  for (int f = threadIdx.x; f < Tcap; f += VA_THREADS)
+    tokmap[(long long)b * Tcap + f] = f < tot ? dur_token_of(cum, N, f) : -1;
+  if (L <= 0) return;
+  // pitch and energy about their means
+  if (on_p || on_e) {  // (block-uniform)
+    for (int t = threadIdx.x; t < L; t += VA_THREADS) {
+      if (on_p) p[t] = fmaf(pr, p[t] - mp, mp) + ps;
+      if (on_e) e[t] = fmaf(er, e[t] - me, me) + es;
+    }
+    __syncthreads();  // the rows below read p' / e' other threads wrote
+  }
+  // embedding add: one wave per valid row, lanes across the channels
+  T* xb = x + (long long)b * Np * D;
+  for (int t = threadIdx.x >> 6; t < L; t += VA_THREADS / 64) {
+    const float pv = p[t], ev = e[t];
+    T* xr = xb + (long long)t * D;
+    for (int c = threadIdx.x & 63; c < D; c += 64) xr[c] = var_embed_chain<T>(xr[c], ev, we[c], be[c], pv, wp[c], bp[c]);
   }
 }
 
@@ -666,6 +806,16 @@ hipError_t launch_var_embed_add(int dt, void* x, int rows, int D, const float* e
                                 const float* p, const float* wp, const float* bp, hipStream_t s) {
   TTS_DISPATCH(dt, hipLaunchKernelGGL(var_embed_add_kernel<TT>, dim3(grid1((long long)rows * D)), dim3(256), 0, s,
                                       (TT*)x, rows, D, e, we, be, p, wp, bp));
+}
+
+hipError_t launch_variance_adapt(int dt, void* x, const float* logd, float* pitch, float* energy, const int* lens,
+                                 const int* override_d, const VarianceCtl& ctl, int B, int N, int Np, int D, int Tcap,
+                                 const float* we, const float* be, const float* wp, const float* bp, int* dur,
+                                 int* mel_lens, int* tokmap, hipStream_t s) {
+  TTS_DISPATCH(dt, hipLaunchKernelGGL(variance_adapt_ctl_kernel<TT>, dim3(B), dim3(VA_THREADS),
+                                      std::max((size_t)(N + 1) * sizeof(int), VA_LDS_MIN), s, (TT*)x, logd, pitch, energy, lens, override_d,
+                                      ctl.duration_scale, ctl.pitch_shift, ctl.pitch_range, ctl.energy_shift,
+                                      ctl.energy_range, N, Np, D, Tcap, we, be, wp, bp, dur, mel_lens, tokmap));
 }
 
 hipError_t launch_regulate(int dt_in, int dt, const void* enc, int B, int N, int D, const int* tokmap, int Tcap,

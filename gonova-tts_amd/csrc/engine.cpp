@@ -917,9 +917,14 @@ int tts_vocoder_context(tts_engine* eng, int* left, int* right) {
   }
 }
 
-int tts_acoustic_forward_spk(tts_engine* eng, const int32_t* d_tokens, const int32_t* d_tok_lens, int B, int N,
-                             const int32_t* d_dur_override, const float* d_spk_emb, int spk_dim, float* d_mel,
-                             int32_t* d_mel_lens, int Tcap, int32_t* d_durations, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// tts_acoustic_forward_spk / _ctl: ctl null = the plain variance adaptor launches
+int acoustic_forward_any(tts_engine* eng, const int32_t* d_tokens, const int32_t* d_tok_lens, int B, int N,
+                         const int32_t* d_dur_override, const float* d_spk_emb, int spk_dim, float* d_mel,
+                         int32_t* d_mel_lens, int Tcap, int32_t* d_durations, const VarianceCtl* ctl, void* stream) {
   return guarded(eng, [&] {
     if (!eng->finalized) throw TtsError(TTS_ERR_STATE, "finalize first");
     if (!eng->ac.loaded) throw TtsError(TTS_ERR_STATE, "acoustic weights not loaded");
@@ -929,8 +934,47 @@ int tts_acoustic_forward_spk(tts_engine* eng, const int32_t* d_tokens, const int
       throw TtsError(TTS_ERR_INVALID, "speaker embedding size does not match the model's projection");
     tts_engine::CallOrder order(eng, (hipStream_t)stream);
     eng->ac.forward(d_tokens, d_tok_lens, B, N, d_dur_override, d_mel, d_mel_lens, Tcap, d_durations, d_spk_emb,
-                    (hipStream_t)stream);
+                    (hipStream_t)stream, ctl);
   });
+}
+
+// the first ctl_size bytes of a caller's tts_prosody (an older header's shorter struct: the
+// missing controls neutral) -> the kernels' struct
+bool read_prosody(const tts_prosody* ctl, size_t ctl_size, VarianceCtl* out) {
+  if (ctl_size > sizeof(tts_prosody) || ctl_size % sizeof(const float*) != 0) return false;
+  tts_prosody c{};
+  std::memcpy(&c, ctl, ctl_size);
+  out->duration_scale = c.duration_scale;
+  out->pitch_shift = c.pitch_shift;
+  out->pitch_range = c.pitch_range;
+  out->energy_shift = c.energy_shift;
+  out->energy_range = c.energy_range;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tts_acoustic_forward_spk(tts_engine* eng, const int32_t* d_tokens, const int32_t* d_tok_lens, int B, int N,
+                             const int32_t* d_dur_override, const float* d_spk_emb, int spk_dim, float* d_mel,
+                             int32_t* d_mel_lens, int Tcap, int32_t* d_durations, void* stream) {
+  return acoustic_forward_any(eng, d_tokens, d_tok_lens, B, N, d_dur_override, d_spk_emb, spk_dim, d_mel, d_mel_lens,
+                              Tcap, d_durations, nullptr, stream);
+}
+
+int tts_acoustic_forward_ctl(tts_engine* eng, const int32_t* d_tokens, const int32_t* d_tok_lens, int B, int N,
+                             const int32_t* d_dur_override, const float* d_spk_emb, int spk_dim, float* d_mel,
+                             int32_t* d_mel_lens, int Tcap, int32_t* d_durations, const tts_prosody* ctl,
+                             size_t ctl_size, void* stream) {
+  VarianceCtl vc;
+  if (ctl && !read_prosody(ctl, ctl_size, &vc)) {
+    g_last_error = "tts_prosody of " + std::to_string(ctl_size) + " bytes: not a whole struct of this library's " +
+                   std::to_string(sizeof(tts_prosody)) + " bytes or an older, shorter one";
+    return TTS_ERR_INVALID;
+  }
+  return acoustic_forward_any(eng, d_tokens, d_tok_lens, B, N, d_dur_override, d_spk_emb, spk_dim, d_mel, d_mel_lens,
+                              Tcap, d_durations, ctl ? &vc : nullptr, stream);
 }
 
 int tts_acoustic_forward(tts_engine* eng, const int32_t* d_tokens, const int32_t* d_tok_lens, int B, int N,
@@ -1388,6 +1432,26 @@ int tts_op_var_embed_add(int dtype, void* x, int rows, int D, const float* e, co
     op_require(x && e && we && be && p && wp && bp, "var_embed_add", "null buffer");
     op_require(rows > 0 && D > 0, "var_embed_add", "needs rows, D > 0" + op_dims({{"rows", rows}, {"D", D}}));
     HIP_CHECK(launch_var_embed_add(dtype, x, rows, D, e, we, be, p, wp, bp, (hipStream_t)stream));
+  });
+}
+
+int tts_op_variance_adapt(int dtype, void* x, const float* logd, float* pitch, float* energy, const int32_t* lens,
+                          int B, int N, int Np, int D, const int32_t* override_d, const tts_prosody* ctl,
+                          size_t ctl_size, const float* we, const float* be, const float* wp, const float* bp, int Tcap,
+                          int32_t* dur, int32_t* mel_lens, int32_t* tokmap, void* stream) {
+  return op_guard([&] {
+    op_dtype(dtype, "variance_adapt");
+    op_require(x && (logd || override_d) && pitch && energy && lens && we && be && wp && bp && dur && mel_lens && tokmap,
+               "variance_adapt", "null buffer");
+    op_require(B > 0 && N > 0 && D > 0 && Tcap > 0, "variance_adapt",
+               "needs B, N, D, Tcap > 0" + op_dims({{"B", B}, {"N", N}, {"D", D}, {"Tcap", Tcap}}));
+    op_require(Np >= N, "variance_adapt", "needs Np >= N" + op_dims({{"N", N}, {"Np", Np}}));
+    op_require(((long long)N + 1) * (long long)sizeof(int) <= 64 * 1024, "variance_adapt",
+               "N " + std::to_string(N) + " above the kernel's 16383 tokens (its prefix sums live in LDS)");
+    VarianceCtl vc;
+    op_require(!ctl || read_prosody(ctl, ctl_size, &vc), "variance_adapt", "bad tts_prosody size");
+    HIP_CHECK(launch_variance_adapt(dtype, x, logd, pitch, energy, lens, override_d, vc, B, N, Np, D, Tcap, we, be, wp,
+                                    bp, dur, mel_lens, tokmap, (hipStream_t)stream));
   });
 }
 

@@ -72,6 +72,73 @@ class TtsConvExt(ctypes.Structure):
     ]
 
 
+class TtsProsody(ctypes.Structure):
+    """tts_prosody: five device float32 [B] arrays, NULL = neutral for every utterance."""
+    _fields_ = [("duration_scale", ctypes.c_void_p), ("pitch_shift", ctypes.c_void_p),
+                ("pitch_range", ctypes.c_void_p), ("energy_shift", ctypes.c_void_p),
+                ("energy_range", ctypes.c_void_p)]
+
+
+# the controls in tts_prosody's order, with their neutral values
+PROSODY_FIELDS = ("duration_scale", "pitch_shift", "pitch_range", "energy_shift", "energy_range")
+PROSODY_NEUTRAL = (1.0, 0.0, 1.0, 0.0, 1.0)
+
+
+def pack_prosody(prosody, B: int) -> Optional[np.ndarray]:
+    """Per-utterance prosody controls -> float32 [5, B] in tts_prosody's order, or None when every
+    utterance is neutral.  `prosody`: None; a dict (or an object with those attributes) of
+    PROSODY_FIELDS names -> scalar or [B] values, missing names neutral; or a list of B entries,
+    each None (neutral) or such a dict of scalars.  Checked here, on the host, before any GPU
+    work: an unknown name, a shape other than [B], a value that is not finite or a
+    duration_scale <= 0 raises ValueError."""
+    if prosody is None:
+        return None
+    out = np.empty((5, B), np.float32)
+    out[:] = np.asarray(PROSODY_NEUTRAL, np.float32)[:, None]
+
+    def fields(p):
+        if isinstance(p, dict):
+            unknown = set(p) - set(PROSODY_FIELDS)
+            if unknown:
+                raise ValueError(f"prosody: unknown control {sorted(unknown)[0]!r} (known: {', '.join(PROSODY_FIELDS)})")
+            return p
+        got = {k: getattr(p, k) for k in PROSODY_FIELDS if hasattr(p, k)}
+        if not got:
+            raise ValueError(f"prosody: expected a dict of {', '.join(PROSODY_FIELDS)}, got {type(p).__name__}")
+        return got
+
+    if isinstance(prosody, (list, tuple)):
+        if len(prosody) != B:
+            raise ValueError(f"prosody: {len(prosody)} entries for a batch of {B}")
+        for b, p in enumerate(prosody):
+            for k, v in (fields(p) if p is not None else {}).items():
+                v = np.asarray(_host(v), np.float64)
+                if v.size != 1:
+                    raise ValueError(f"prosody[{b}].{k}: expected one value, got shape {v.shape}")
+                out[PROSODY_FIELDS.index(k), b] = np.float32(v.reshape(()))
+    else:
+        for k, v in fields(prosody).items():
+            if v is None:
+                continue
+            v = np.asarray(_host(v), np.float64)
+            if v.ndim and v.shape != (B,):
+                raise ValueError(f"prosody.{k}: shape {v.shape}, expected ({B},)")
+            out[PROSODY_FIELDS.index(k)] = v.astype(np.float32)
+    for i, k in enumerate(PROSODY_FIELDS):
+        if not np.isfinite(out[i]).all():
+            raise ValueError(f"prosody.{k}: values must be finite")
+    if not (out[0] > 0).all():
+        raise ValueError("prosody.duration_scale: values must be positive")
+    if (out == np.asarray(PROSODY_NEUTRAL, np.float32)[:, None]).all():
+        return None
+    return out
+
+
+def _host(v):
+    """A control value as the host sees it (a device tensor is read back: validation is on the host)."""
+    return v.detach().cpu().numpy() if hasattr(v, "detach") else v
+
+
 # every function declared in include/tts_hip.h: (name, restype, argtypes)
 _VP, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 C_API = [
@@ -89,6 +156,8 @@ C_API = [
     ("tts_vocoder_context", _I, [_VP, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ("tts_acoustic_forward", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP]),
     ("tts_acoustic_forward_spk", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP]),
+    ("tts_acoustic_forward_ctl", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _VP,
+                                      ctypes.POINTER(TtsProsody), ctypes.c_size_t, _VP]),
     ("tts_acoustic_speaker_dim", _I, [_VP, ctypes.POINTER(ctypes.c_int)]),
     ("tts_acoustic_range_flag", _I, [_VP, _VP, _VP]),
     ("tts_acoustic_set_precision", _I, [_VP, _I]),
@@ -122,6 +191,8 @@ C_API = [
     ("tts_op_glu_dwconv", _I, [_I, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP]),
     ("tts_op_durations", _I, [_VP, _VP, _I, _I, _VP, _F, _I, _VP, _VP, _VP, _VP]),
     ("tts_op_var_embed_add", _I, [_I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("tts_op_variance_adapt", _I, [_I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, ctypes.POINTER(TtsProsody),
+                                   ctypes.c_size_t, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
     ("tts_op_regulate", _I, [_I, _I, _VP, _I, _I, _I, _VP, _I, _I, _I, _F, _VP, _VP]),
     ("tts_op_mel_out", _I, [_I, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
     ("tts_op_spk_bias", _I, [_I, _VP, _I, _I, _VP, _VP, _I, _VP, _VP]),
@@ -441,12 +512,16 @@ class HipEngine:
             self.set_encoder_precision("exact")
 
     def acoustic(self, tokens, tok_lens, t_cap: int, durations=None, stream=None, return_durations=False,
-                 speaker_embedding=None, return_range=False):
+                 speaker_embedding=None, return_range=False, prosody=None):
         """tokens: cuda int32 [B, N]; returns (mel [B, t_cap, 80] f32, mel_lens int32 [B]).
         speaker_embedding: optional float32 [B, E] (HF:1192-1196), E = speaker_dim.
         return_range: also return the range word of this forward (cuda int32 [1], nonzero when a
         split-precision operand was outside f16's range; None without the guard), enqueued on the
-        same stream -- read it at the next host sync."""
+        same stream -- read it at the next host sync.
+        prosody: per-utterance controls (pack_prosody's forms, checked on the host: ValueError), or
+        a cuda float32 [5, B] block in PROSODY_FIELDS order that a caller has packed, checked and
+        uploaded with its other inputs (model.py).  All neutral (or None): the plain forward;
+        otherwise tts_acoustic_forward_ctl, whose variance adaptor is one fused launch."""
         import torch
         tokens = tokens.to(dtype=torch.int32).contiguous()
         tok_lens = tok_lens.to(device=tokens.device, dtype=torch.int32).contiguous()
@@ -469,11 +544,21 @@ class HipEngine:
             speaker_embedding = torch.as_tensor(speaker_embedding, dtype=torch.float32).to(tokens.device)
             speaker_embedding = speaker_embedding.reshape(B, -1).contiguous()
             sptr, sdim = ctypes.c_void_p(speaker_embedding.data_ptr()), speaker_embedding.shape[1]
-        check(self.lib.tts_acoustic_forward_spk(self.handle, ctypes.c_void_p(tokens.data_ptr()),
-                                                ctypes.c_void_p(tok_lens.data_ptr()), B, N, dptr, sptr, sdim,
-                                                ctypes.c_void_p(mel.data_ptr()), ctypes.c_void_p(mel_lens.data_ptr()),
-                                                t_cap, ctypes.c_void_p(dur_out.data_ptr()), _stream_ptr(stream)),
-              "tts_acoustic_forward")
+        ctl = self._prosody_block(prosody, B, tokens.device, stream)
+        if ctl is None:
+            check(self.lib.tts_acoustic_forward_spk(self.handle, ctypes.c_void_p(tokens.data_ptr()),
+                                                    ctypes.c_void_p(tok_lens.data_ptr()), B, N, dptr, sptr, sdim,
+                                                    ctypes.c_void_p(mel.data_ptr()), ctypes.c_void_p(mel_lens.data_ptr()),
+                                                    t_cap, ctypes.c_void_p(dur_out.data_ptr()), _stream_ptr(stream)),
+                  "tts_acoustic_forward")
+        else:
+            cs = prosody_struct(ctl)
+            check(self.lib.tts_acoustic_forward_ctl(self.handle, ctypes.c_void_p(tokens.data_ptr()),
+                                                    ctypes.c_void_p(tok_lens.data_ptr()), B, N, dptr, sptr, sdim,
+                                                    ctypes.c_void_p(mel.data_ptr()), ctypes.c_void_p(mel_lens.data_ptr()),
+                                                    t_cap, ctypes.c_void_p(dur_out.data_ptr()), ctypes.byref(cs),
+                                                    ctypes.sizeof(cs), _stream_ptr(stream)),
+                  "tts_acoustic_forward_ctl")
         rw = None
         # the word is copied out and cleared only for a caller that reads it: otherwise it keeps
         # accumulating, so the next caller that asks sees an earlier unread overflow too (a spurious
@@ -484,6 +569,24 @@ class HipEngine:
                   "tts_acoustic_range_flag")
         out = (mel, mel_lens, dur_out) if return_durations else (mel, mel_lens)
         return out + (rw,) if return_range else out
+
+    @staticmethod
+    def _prosody_block(prosody, B, dev, stream):
+        """acoustic()'s `prosody` -> cuda float32 [5, B] (None: neutral, the plain forward)."""
+        import torch
+        if prosody is None:
+            return None
+        if isinstance(prosody, torch.Tensor) and prosody.is_cuda:
+            if prosody.dtype != torch.float32 or tuple(prosody.shape) != (5, B):
+                raise ValueError(f"prosody block: {prosody.dtype} {tuple(prosody.shape)}, expected float32 (5, {B})")
+            return prosody.contiguous()
+        host = pack_prosody(prosody, B)
+        if host is None:
+            return None
+        pinned = torch.empty((5, B), dtype=torch.float32, pin_memory=True)
+        pinned.numpy()[:] = host
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return pinned.to(dev, non_blocking=True)
 
     def profile(self, enable: bool = True):
         check(self.lib.tts_engine_profile(self.handle, int(enable)), "profile")
@@ -645,6 +748,25 @@ def durations_op(logd, lens, B, N, Tcap, dur, mel_lens, tokmap, override_d=None,
 def var_embed_add_op(dtype, x, rows, D, e, we, be, p, wp, bp, stream=None):
     check(load_library().tts_op_var_embed_add(DTYPES[dtype], _p(x), rows, D, _p(e), _p(we), _p(be), _p(p), _p(wp), _p(bp),
                                               _stream_ptr(stream)), "tts_op_var_embed_add")
+
+
+def prosody_struct(block) -> TtsProsody:
+    """tts_prosody over the rows of a cuda float32 [5, B] block (PROSODY_FIELDS order; None: all NULL)."""
+    cs = TtsProsody()
+    if block is not None:
+        for i, k in enumerate(PROSODY_FIELDS):
+            setattr(cs, k, block[i].data_ptr())
+    return cs
+
+
+def variance_adapt_op(dtype, x, logd, pitch, energy, lens, B, N, Np, D, we, be, wp, bp, Tcap, dur, mel_lens, tokmap,
+                      override_d=None, ctl=None, stream=None):
+    """ctl: None (NULL struct), a TtsProsody, or a cuda float32 [5, B] block."""
+    cs = ctl if isinstance(ctl, TtsProsody) or ctl is None else prosody_struct(ctl)
+    check(load_library().tts_op_variance_adapt(
+        DTYPES[dtype], _p(x), _p(logd), _p(pitch), _p(energy), _p(lens), B, N, Np, D, _p(override_d),
+        None if cs is None else ctypes.byref(cs), 0 if cs is None else ctypes.sizeof(cs), _p(we), _p(be), _p(wp),
+        _p(bp), Tcap, _p(dur), _p(mel_lens), _p(tokmap), _stream_ptr(stream)), "tts_op_variance_adapt")
 
 
 def regulate_op(dtype_in, dtype, enc, B, N, D, tokmap, Tcap, frames, Tout, scale, out, stream=None):

@@ -8,9 +8,12 @@ and a float32 cast (`:352-357`).  `GonovaTTS` keeps exactly that duck-typed surf
  and adds `generate_batch` for many sentences at once.
 
 Semantics of the extra arguments: the FastSpeech2 + HiFi-GAN pipeline is
-deterministic and has no voice cloning, so `audio_prompt_path`, `exaggeration`,
-`cfg_weight` and `temperature` are accepted and ignored (the reference forwards a
-possibly unsanitised path, `voice_manager.py:166-177`; it is never opened here).
+deterministic and has no voice cloning, so `cfg_weight` and `temperature` are accepted
+and ignored, and `audio_prompt_path` only selects a stored speaker embedding (the
+reference forwards a possibly unsanitised path, `voice_manager.py:166-177`; an audio
+prompt is never opened here).  `exaggeration` sets the range of the predicted pitch and
+energy contours (0.5 neutral), and `speed`, `pitch` and `energy` are this model's own
+prosody controls (prosody.py), applied per utterance on the device.
 Output rate is `self.sr` = 22,050 Hz (the reference hard-codes 24 kHz,
 `synthesizer.py:119`).
 """
@@ -25,7 +28,8 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from .config import AcousticConfig, VocoderConfig, SAMPLE_RATE, vocoder_context_frames
-from .engine import HipEngine, resample_chunk_counts, resample_history
+from .engine import HipEngine, PROSODY_NEUTRAL, pack_prosody, resample_chunk_counts, resample_history
+from .prosody import prosody_controls  # noqa: F401  (public here too)
 from .text import tokenize_batch
 from .weights import make_acoustic_weights, make_vocoder_weights
 
@@ -122,8 +126,32 @@ class GonovaTTS:
         return cls(eng, acfg, vcfg, sample_rate=sample_rate)
 
     # -------------------------------------------------------------- synthesis
+    def _controls(self, prosody, B: int, lens, durations):
+        """A call's `prosody` (engine.pack_prosody's forms) -> (float32 [5, B] block or None when
+        all neutral, durations, largest duration_scale).  Given durations are scaled here, on the
+        host, with the kernel's float32 rint, and go down with a neutral scale: the host then knows
+        the frame counts (_mel_lens_host) exactly as the device computes them."""
+        ctl = pack_prosody(prosody, B)
+        if ctl is None:
+            return None, durations, 1.0
+        smax = float(ctl[0].max()) if B else 1.0
+        if durations is not None:
+            durations = scale_durations(durations, ctl[0])
+            ctl = ctl.copy()
+            ctl[0] = 1.0
+            smax = 1.0
+            if (ctl == np.asarray(PROSODY_NEUTRAL, np.float32)[:, None]).all():
+                ctl = None
+        return ctl, durations, smax
+
+    def _frame_budget(self, N: int, smax: float = 1.0) -> int:
+        """First-pass frame budget with predicted durations: 12 frames per token, times the
+        batch's largest duration_scale when that is above 1 (exact retry if exceeded)."""
+        return max(64, int(np.ceil(self.FRAMES_PER_TOKEN_CAP * N * max(1.0, smax))))
+
     def synthesize_tokens(self, tokens: np.ndarray, lens: np.ndarray, durations: Optional[np.ndarray] = None,
-                          stream=None, speaker_embedding: Optional[np.ndarray] = None, host_lens: bool = True):
+                          stream=None, speaker_embedding: Optional[np.ndarray] = None, host_lens: bool = True,
+                          prosody=None):
         """tokens int32 [B, N], lens [B] -> (wav cuda float32 [B, T*hop], wav_lens np.int64 [B]).
         host_lens=False makes no host sync, so a caller can queue several batches back to back
         (dist.ShardedSynthesis), and returns (wav, wav_lens cuda int64 [B], pending): `pending` is
@@ -133,15 +161,21 @@ class GonovaTTS:
         Range guard (include/tts_hip.h, ABI 4): with the exact encoder of a 16-bit model the
         acoustic forward's range word travels with the one host read this path makes anyway; when a
         split-precision operand was outside f16's range the batch is synthesized again with the
-        encoder on the exact fp32 MFMA kernels (`range_fallbacks` counts these)."""
+        encoder on the exact fp32 MFMA kernels (`range_fallbacks` counts these); the rerun keeps the
+        controls.
+
+        prosody: per-utterance controls in any of engine.pack_prosody's forms (None: neutral);
+        a bad value raises ValueError before any GPU work."""
         import torch
         dev = self.engine.torch_device
         B, N = tokens.shape
-        tok, tl, dd = _upload_i32((tokens, lens, durations), dev, stream)
-        t_cap = max(64, int(self.FRAMES_PER_TOKEN_CAP * N))
+        ctl, durations, smax = self._controls(prosody, B, lens, durations)
+        tok, tl, dd, cb = _upload_i32((tokens, lens, durations, _as_i32(ctl)), dev, stream)
+        cb = None if cb is None else cb.view(torch.float32)
+        t_cap = self._frame_budget(N, smax)
         if durations is not None:
             t_cap = max(1, int(np.asarray(durations).sum(axis=1).max()))
-        args = (tok, tl, dd, t_cap, stream, speaker_embedding, host_lens)
+        args = (tok, tl, dd, t_cap, stream, speaker_embedding, host_lens, cb)
         # the engine's device is the current one for this thread (the streams torch hands out, the
         # ops below): an executor thread of a multi-GPU service starts on device 0
         with torch.cuda.device(self.engine.device_index):
@@ -151,7 +185,7 @@ class GonovaTTS:
                     wav, wav_lens, _ = self._synthesize_once(*args)
                 tripped = None
             if not host_lens:  # tripped: the unread range word (device) or None; the caller reads it
-                pend = PendingRange(self, args[:-1] + (True,), tripped) if isinstance(tripped, torch.Tensor) else None
+                pend = PendingRange(self, args[:6] + (True, cb), tripped) if isinstance(tripped, torch.Tensor) else None
                 return wav, wav_lens, pend
         return wav, wav_lens
 
@@ -170,13 +204,14 @@ class GonovaTTS:
         with self.engine.encoder_f32():
             yield
 
-    def _synthesize_once(self, tok, tl, dd, t_cap, stream, spk, host_lens):
+    def _synthesize_once(self, tok, tl, dd, t_cap, stream, spk, host_lens, ctl=None):
         """-> (wav, wav_lens, range guard tripped: bool, or None when nothing was read); with
         host_lens=False the third item is the forward's range word itself (cuda int32 [1], None
-        without the guard), unread"""
+        without the guard), unread.  ctl: the controls' device block (cuda float32 [5, B]) or None"""
         import torch
         mel, mel_lens, dur, rw = self.engine.acoustic(tok, tl, t_cap, durations=dd, stream=stream,
-                                                      return_durations=True, speaker_embedding=spk, return_range=True)
+                                                      return_durations=True, speaker_embedding=spk, return_range=True,
+                                                      prosody=ctl)
         lens_known = None
         tripped = None
         if dd is None:
@@ -185,9 +220,10 @@ class GonovaTTS:
             if tripped:
                 return None, None, True
             if need > t_cap:  # exact second pass with the predicted durations and a fitting cap
+                # (they are scaled already: the second pass runs with a neutral duration_scale)
                 mel, mel_lens, dur, rw = self.engine.acoustic(tok, tl, need, durations=dur, stream=stream,
                                                               return_durations=True, speaker_embedding=spk,
-                                                              return_range=True)
+                                                              return_range=True, prosody=_unit_scale(ctl))
                 need, lens_known, tripped = _need_and_lens(dur, mel_lens, rw)
                 if tripped:
                     return None, None, True
@@ -243,7 +279,8 @@ class GonovaTTS:
 
     def stream_tokens(self, tokens: np.ndarray, lens: np.ndarray, chunk_frames: int = 32,
                       context: Optional[int] = None, durations: Optional[np.ndarray] = None, stream=None,
-                      speaker_embedding: Optional[np.ndarray] = None, output_rate: Optional[int] = None):
+                      speaker_embedding: Optional[np.ndarray] = None, output_rate: Optional[int] = None,
+                      prosody=None):
         """Sub-sentence streaming: one acoustic pass, then the vocoder
         runs on windows [c0 - ctx, c0 + chunk + ctx) and keeps the middle `chunk` frames.
         With ctx >= the receptive field every kept sample is computed from the same inputs
@@ -259,16 +296,17 @@ class GonovaTTS:
         carries the filter's history between chunks; wav_chunk is then [B, cap] at that rate with
         cap = ceil(chunk*hop*up/down) + n_flush, and the valid counts differ from chunk to chunk
         (an utterance's last chunk also brings the outputs held back until its end is known).  The
-        valid parts concatenate to synthesize_tokens' output at that rate, bit for bit."""
+        valid parts concatenate to synthesize_tokens' output at that rate, bit for bit.
+        prosody: as synthesize_tokens'; with the same controls the two agree bit for bit."""
         import torch
         context = self._context(context)
         with torch.cuda.device(self.engine.device_index):  # (see synthesize_tokens)
             for c0, wav, valid, _ in self._stream_tokens(tokens, lens, chunk_frames, context, durations, stream,
-                                                         speaker_embedding, output_rate):
+                                                         speaker_embedding, output_rate, prosody):
                 yield c0, wav, valid
 
     def _stream_tokens(self, tokens, lens, chunk_frames, context, durations, stream, speaker_embedding,
-                       output_rate=None):
+                       output_rate=None, prosody=None):
         """stream_tokens' generator; yields a fourth item, ended np bool [B]: the utterance has no
         frame past this chunk."""
         import torch
@@ -279,12 +317,14 @@ class GonovaTTS:
         rs = None
         if output_rate and int(output_rate) != self.native_sr:
             rs = _ChunkResampler(self.engine, B, int(output_rate), self.native_sr, hop, chunk_frames, dev, stream)
-        tok, tl, dd = _upload_i32((tokens, lens, durations), dev, stream)
-        t_cap = max(64, int(self.FRAMES_PER_TOKEN_CAP * N)) if durations is None else \
+        ctl, durations, smax = self._controls(prosody, B, lens, durations)
+        tok, tl, dd, cb = _upload_i32((tokens, lens, durations, _as_i32(ctl)), dev, stream)
+        cb = None if cb is None else cb.view(torch.float32)
+        t_cap = self._frame_budget(N, smax) if durations is None else \
             max(1, int(np.asarray(durations).sum(axis=1).max()))
         spk = speaker_embedding
         mel, mel_lens, dur, rw = self.engine.acoustic(tok, tl, t_cap, durations=dd, stream=stream, return_durations=True,
-                                                      speaker_embedding=spk, return_range=True)
+                                                      speaker_embedding=spk, return_range=True, prosody=cb)
         first = None  # (window end, kept frames, chunk) enqueued ahead of the host read
         if durations is None:
             # The first chunk's window needs no host value when the longest utterance covers it
@@ -311,21 +351,23 @@ class GonovaTTS:
                 first, fell_back = None, True
                 with self._range_fallback():
                     mel, mel_lens, dur = self.engine.acoustic(tok, tl, t_cap, durations=None, stream=stream,
-                                                              return_durations=True, speaker_embedding=spk)
+                                                              return_durations=True, speaker_embedding=spk, prosody=cb)
                 need, lens_h, _ = _need_and_lens(dur, mel_lens)
             if need > t_cap:
                 first = None
                 # after a fallback the second pass stays on the fp32 encoder: its activations do not
                 # depend on the durations, so the split encoder would overflow again
                 with (self.engine.encoder_f32() if fell_back else nullcontext()):
+                    # (dur is scaled already: a neutral duration_scale from here on)
                     mel, mel_lens, dur, rw = self.engine.acoustic(tok, tl, need, durations=dur, stream=stream,
                                                                   return_durations=True, speaker_embedding=spk,
-                                                                  return_range=True)
+                                                                  return_range=True, prosody=_unit_scale(cb))
                 need, lens_h, tripped = _need_and_lens(dur, mel_lens, rw)
                 if tripped and not fell_back:
                     with self._range_fallback():
                         mel, mel_lens, dur = self.engine.acoustic(tok, tl, need, durations=dur, stream=stream,
-                                                                  return_durations=True, speaker_embedding=spk)
+                                                                  return_durations=True, speaker_embedding=spk,
+                                                                  prosody=_unit_scale(cb))
                     need, lens_h, _ = _need_and_lens(dur, mel_lens)
         else:
             # given durations fix the frame counts on the host: no device sync between the
@@ -351,7 +393,7 @@ class GonovaTTS:
                 if int(rw.item()) != 0:
                     with self._range_fallback():
                         mel, mel_lens = self.engine.acoustic(tok, tl, t_cap, durations=dd, stream=stream,
-                                                             speaker_embedding=spk)
+                                                             speaker_embedding=spk, prosody=cb)
                     win = mel[:, w0:w1].contiguous()
                     win_lens = torch.clamp(mel_lens - w0, min=0, max=w1 - w0).to(torch.int32)
                     wav = self.engine.vocoder_chunk(win, win_lens, c0 - w0, tc, stream=stream)
@@ -379,23 +421,26 @@ class GonovaTTS:
         return groups
 
     def stream_batch(self, texts: List[str], chunk_frames: int = 32,
-                     speaker_embeddings: Optional[List[Optional[np.ndarray]]] = None):
+                     speaker_embeddings: Optional[List[Optional[np.ndarray]]] = None,
+                     prosody: Optional[List[Optional[dict]]] = None):
         """Sub-sentence streaming of many sentences in one batched pass (the service's opt-in
         `stream_frames` mode): yields, per vocoder chunk, a list of (sentence index, float32
         samples of that chunk, sentence finished).  A sentence's pieces concatenate to the
         stream_tokens output, which equals the full pass (stream_tokens) -- at `sr`: with an
         output rate other than the vocoder's the chunks come through the chunked resampler
         (stream_tokens(output_rate=sr)) and the pieces concatenate to generate_batch's audio at
-        that rate, bit for bit; their lengths then differ from chunk to chunk."""
+        that rate, bit for bit; their lengths then differ from chunk to chunk.
+        prosody: optional per-sentence controls (None entries: neutral), as generate_batch's."""
         if not texts:
             return
+        _check_per_sentence(prosody, len(texts))
         import torch
         with self._lock, torch.cuda.device(self.engine.device_index):
             for idx, spk in self._voice_groups(len(texts), speaker_embeddings):
                 tokens, lens = tokenize_batch([texts[i] for i in idx])
                 done = [False] * len(idx)
                 for c0, wav, valid, ended in self._stream_tokens(tokens, lens, chunk_frames, None, None, None, spk,
-                                                                 self.sr):
+                                                                 self.sr, _pick(prosody, idx)):
                     host = _to_host(wav)
                     out = []
                     for r, i in enumerate(idx):
@@ -411,17 +456,22 @@ class GonovaTTS:
                     yield last
 
     def generate_batch(self, texts: List[str], speaker_embeddings: Optional[List[Optional[np.ndarray]]] = None,
-                       **_ignored) -> List[np.ndarray]:
+                       prosody: Optional[List[Optional[dict]]] = None, **_ignored) -> List[np.ndarray]:
         """Synthesize many sentences in one batched pass -> list of float32 waveforms.
-        speaker_embeddings: optional per-sentence voice vectors (None entries: no voice)."""
+        speaker_embeddings: optional per-sentence voice vectors (None entries: no voice).
+        prosody: optional per-sentence controls, each None (neutral) or a dict of
+        engine.PROSODY_FIELDS scalars (prosody_controls builds one from speed / pitch / energy /
+        exaggeration); sentences with different controls share the one pass."""
         if not texts:
             return []
+        _check_per_sentence(prosody, len(texts))
         groups = self._voice_groups(len(texts), speaker_embeddings)
         out: List[Optional[np.ndarray]] = [None] * len(texts)
         with self._lock:
             for idx, spk in groups:
                 tokens, lens = tokenize_batch([texts[i] for i in idx])
-                wav, wav_lens = self.synthesize_tokens(tokens, lens, speaker_embedding=spk)
+                wav, wav_lens = self.synthesize_tokens(tokens, lens, speaker_embedding=spk,
+                                                       prosody=_pick(prosody, idx))
                 host = _to_host(wav)
                 for r, i in enumerate(idx):
                     out[i] = host[r, : int(wav_lens[r])].astype(np.float32, copy=False)
@@ -455,20 +505,64 @@ class GonovaTTS:
         return v
 
     def generate(self, text: str, audio_prompt_path: Optional[str] = None, exaggeration: float = 0.5,
-                 cfg_weight: float = 0.5, temperature: float = 0.8, **kwargs):
-        """Same call shape as the reference's `model.generate` (synthesizer.py:344-350).
+                 cfg_weight: float = 0.5, temperature: float = 0.8, speed: float = 1.0, pitch: float = 0.0,
+                 energy: float = 0.0, **kwargs):
+        """Same call shape as the reference's `model.generate` (synthesizer.py:344-350), plus the
+        prosody controls: speed (speaking rate, 0.25..4), pitch and energy (shifts in the
+        predictors' normalised units, -4..4) and exaggeration (0.5 neutral; the pitch and energy
+        ranges are clip(2 * exaggeration, 0, 4)) -- prosody_controls; a value outside its range
+        raises ValueError.  cfg_weight and temperature stay ignored: the model is deterministic.
 
         Returns a float32 torch tensor of shape (1, N) on the engine device; the
         reference's `audio.squeeze().cpu().numpy()` applies unchanged.  audio_prompt_path
         selects a stored speaker embedding on a multi-speaker model (speaker_embedding())."""
         import torch
-        del exaggeration, cfg_weight, temperature, kwargs
+        del cfg_weight, temperature, kwargs
+        ctl = prosody_controls(speed=speed, pitch=pitch, energy=energy, exaggeration=exaggeration)
         spk = self.speaker_embedding(audio_prompt_path)
         with self._lock:
             tokens, lens = tokenize_batch([text])
             wav, wav_lens = self.synthesize_tokens(tokens, lens,
-                                                   speaker_embedding=None if spk is None else spk[None])
+                                                   speaker_embedding=None if spk is None else spk[None],
+                                                   prosody=None if ctl is None else [ctl])
         return wav[:, : int(wav_lens[0])].contiguous().to(torch.float32)
+
+
+def scale_durations(durations, scale) -> np.ndarray:
+    """Given durations under per-utterance duration_scale values, as the kernel computes them:
+    rint(float32(max(d, 0)) * float32(scale)), ties to even; a scale of 1 leaves d as it is."""
+    d = np.maximum(np.asarray(durations, np.int64), 0)
+    sc = np.asarray(scale, np.float32).reshape(-1, 1)
+    scaled = np.rint(d.astype(np.float32) * sc).astype(np.int64)
+    return np.where(sc == np.float32(1), np.asarray(durations, np.int64), scaled).astype(np.int32)
+
+
+def _as_i32(ctl):
+    """The controls' float32 block as the int32 words _upload_i32 carries (None passes through)."""
+    return None if ctl is None else np.ascontiguousarray(ctl, np.float32).view(np.int32)
+
+
+def _unit_scale(cb):
+    """The controls' device block with a neutral duration_scale (the exact second pass feeds
+    durations that are scaled already); None passes through."""
+    if cb is None:
+        return None
+    cb = cb.clone()
+    cb[0] = 1.0
+    return cb
+
+
+def _check_per_sentence(prosody, n: int):
+    if prosody is not None and len(prosody) != n:
+        raise ValueError(f"prosody: {len(prosody)} entries for {n} sentences")
+
+
+def _pick(prosody, idx):
+    """The per-sentence controls of the sentences idx (None when none of them has any)."""
+    if prosody is None:
+        return None
+    sel = [prosody[i] for i in idx]
+    return None if all(p is None for p in sel) else sel
 
 
 # Alias with the reference's class name so `from gonova_tts_amd.model import ChatterboxTTS`

@@ -47,6 +47,7 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
+from ..prosody import prosody_controls
 from ..text import split_into_sentences
 
 logger = logging.getLogger(__name__)
@@ -75,6 +76,12 @@ class _Item:
 
     def __init__(self, state, j, text, framing, seq):
         self.state, self.j, self.text, self.framing, self.seq = state, j, text, framing, seq
+
+
+def _request_prosody(req) -> Optional[dict]:
+    """A request's controls as the engine's per-utterance dict (None: neutral)."""
+    return prosody_controls(speed=getattr(req, "speed", 1.0), pitch=getattr(req, "pitch", 0.0),
+                            energy=getattr(req, "energy", 0.0), exaggeration=getattr(req, "exaggeration", 0.5))
 
 
 class DynamicBatcher:
@@ -231,6 +238,12 @@ class DynamicBatcher:
         kw = {"speaker_embeddings": voices} if any(v is not None for v in voices) else {}
         frames = batch[0].framing
         try:
+            # per-sentence prosody controls, likewise only when some sentence has any: sentences
+            # of requests with different controls share the batch (the controls are per utterance
+            # on the device), and a neutral batch makes the call it always made
+            prosody = [_request_prosody(it.state.req) for it in batch]
+            if any(p is not None for p in prosody):
+                kw["prosody"] = prosody
             if frames == 0:
                 synth = self.synth_batches[eng]
                 audios = await loop.run_in_executor(None, lambda: synth(texts, **kw))

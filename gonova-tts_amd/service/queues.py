@@ -33,6 +33,11 @@ class SynthesisRequest:
     streaming: bool = True
     voice: Optional[Any] = None  # the voice_id's registered speaker embedding (None: default voice)
     stream_frames: int = 0       # > 0: sub-sentence frames of that many mel frames (opt-in; 0 = per sentence)
+    # prosody controls (prosody.prosody_controls; with exaggeration above): speaking rate, pitch and
+    # energy shifts in the predictors' normalised units
+    speed: float = 1.0
+    pitch: float = 0.0
+    energy: float = 0.0
 
 
 @dataclass
@@ -95,9 +100,10 @@ class TTSQueueManager:
     # ------------------------------------------------------------------ requests
     async def enqueue_request(self, connection_id: str, text: str, voice_id: str = "default", chunk_size: int = 50,
                               exaggeration: float = 0.5, streaming: bool = True, timeout: float = 2.0,
-                              voice: Optional[Any] = None, stream_frames: int = 0) -> bool:
+                              voice: Optional[Any] = None, stream_frames: int = 0, speed: float = 1.0,
+                              pitch: float = 0.0, energy: float = 0.0) -> bool:
         req = SynthesisRequest(connection_id, text, voice_id, time.time(), chunk_size, exaggeration, streaming, voice,
-                               stream_frames)
+                               stream_frames, speed, pitch, energy)
         try:
             # a put that fits starts no timer (wait_for's task and timer handle are a loop hop
             # on every request); a full queue waits up to `timeout`

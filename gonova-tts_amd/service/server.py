@@ -4,6 +4,8 @@
 * `WS /v1/stream/tts` (`server.py:421-444`): per-IP rate limit (100 per 60 s) and a
   connection cap, both rejecting with close code 1008; messages
   `{"type":"synthesize","text",...,"voice_id","chunk_size","exaggeration","streaming"}`
+  (plus the prosody controls `speed`, `pitch`, `energy`; `exaggeration` sets the pitch and
+  energy ranges, 0.5 neutral -- prosody.py)
   (`server.py:215-224`); replies are one binary frame of raw float32 PCM per sentence and
   `{"type":"synthesis_complete","chunk_id":N}` (`server.py:279-286`);
   `register_voice` / `list_voices` answer in the reference's message shapes
@@ -33,6 +35,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
+from ..prosody import prosody_controls
 from .batcher import DynamicBatcher
 from .queues import TTSQueueManager
 
@@ -244,6 +247,10 @@ class TTSService:
                     raise ValueError("stream_frames is not available: this model resamples to "
                                      f"{getattr(self.model, 'sr', None)} Hz per sentence only (no "
                                      "streams_resampled); omit it for one frame per sentence")
+                # prosody controls: numbers, finite, in range (prosody.prosody_controls), or refused
+                ctl = {k: data.get(k, d) for k, d in (("speed", 1.0), ("pitch", 0.0), ("energy", 0.0),
+                                                      ("exaggeration", 0.5))}
+                prosody_controls(**ctl)
             except ValueError as e:
                 # a request refused before it is queued: the client is told (reference error shape,
                 # server.py:244-247), instead of waiting for a marker that never comes
@@ -255,8 +262,9 @@ class TTSService:
             await self.queues.enqueue_request(
                 connection_id=conn_id, text=text, voice_id=vid,
                 chunk_size=data.get("chunk_size", self.chunk_size),
-                exaggeration=data.get("exaggeration", 0.5), streaming=data.get("streaming", True),
-                voice=self.voices.get(vid) if isinstance(vid, str) else None, stream_frames=frames)
+                exaggeration=ctl["exaggeration"], streaming=data.get("streaming", True),
+                voice=self.voices.get(vid) if isinstance(vid, str) else None, stream_frames=frames,
+                speed=ctl["speed"], pitch=ctl["pitch"], energy=ctl["energy"])
         elif kind == "register_voice":
             await ws.send_json(self.register_voice(data))
         elif kind == "list_voices":

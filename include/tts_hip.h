@@ -67,7 +67,8 @@ typedef struct tts_engine tts_engine;
  *      additive: tts_resample_poly_chunk / tts_resample_history (a caller detects them by symbol),
  *      and tts_vocoder_context (the loaded generator's receptive field in mel frames), and the
  *      op-level tts_op_rel_attn / tts_op_rel_attn_ws_bytes, and the op-level
- *      tts_op_conv_layer_create / _destroy / tts_op_conv1d_ex / tts_op_conv_ws_bytes */
+ *      tts_op_conv_layer_create / _destroy / tts_op_conv1d_ex / tts_op_conv_ws_bytes, and per-utterance
+ *      prosody controls: tts_prosody / tts_acoustic_forward_ctl and the op-level tts_op_variance_adapt */
 #define TTS_ABI_VERSION 5
 int tts_abi_version(void);
 
@@ -189,6 +190,38 @@ int tts_acoustic_forward_spk(tts_engine* eng, const int32_t* d_tokens, const int
                              int B, int N, const int32_t* d_dur_override, const float* d_spk_emb,
                              int spk_dim, float* d_mel, int32_t* d_mel_lens, int Tcap,
                              int32_t* d_durations, void* stream);
+/* Per-utterance prosody controls (ABI 5, additive; a caller detects tts_acoustic_forward_ctl by
+ * symbol).  Five device arrays of B float32 each; a NULL array is neutral for every utterance.
+ * Fields are only ever appended: the struct goes by pointer with its size, as tts_config does.
+ * For utterance b with len valid tokens:
+ *   duration_scale  HF's speaking_speed (HF:104-109): d = rint(float(d) * scale), ties to even, after
+ *                   the prediction or the override and before the all-zero rule -- tts_op_durations'
+ *                   `speed`.  Above 1 is slower.  1 skips the multiply; a value that is not positive
+ *                   or not finite counts as 1.
+ *   pitch_range, pitch_shift    p'[t] = m + range * (p[t] - m) + shift on the predicted pitch, in the
+ *                   predictor's normalised units, m the fp32 mean of p over the len valid tokens
+ *                   (summed in an order len alone fixes).  range 1 with shift 0 keeps p bit for bit.
+ *   energy_range, energy_shift  the same on the predicted energy.
+ * An utterance's bits depend on its own tokens and its own controls only -- not on B, its
+ * neighbours or their controls, or on what the predictions hold past its length. */
+typedef struct tts_prosody {
+  const float* duration_scale; /* neutral 1 */
+  const float* pitch_shift;    /* neutral 0 */
+  const float* pitch_range;    /* neutral 1 */
+  const float* energy_shift;   /* neutral 0 */
+  const float* energy_range;   /* neutral 1 */
+} tts_prosody;
+
+/* tts_acoustic_forward_spk with controls: ctl_size = sizeof(tts_prosody) of the caller's header (a
+ * shorter, older struct: the missing controls neutral; a longer one, or a size that is no whole
+ * number of pointers: TTS_ERR_INVALID).  ctl == NULL is tts_acoustic_forward_spk itself, launch for
+ * launch.  With ctl the variance adaptor's durations, the pitch / energy controls and the embedding
+ * add run as one launch in place of three (no launch more than without controls), and the call
+ * stays asynchronous under the same conditions; the range guard and TTS_ENCODER_F32 apply unchanged. */
+int tts_acoustic_forward_ctl(tts_engine* eng, const int32_t* d_tokens, const int32_t* d_tok_lens,
+                             int B, int N, const int32_t* d_dur_override, const float* d_spk_emb,
+                             int spk_dim, float* d_mel, int32_t* d_mel_lens, int Tcap,
+                             int32_t* d_durations, const tts_prosody* ctl, size_t ctl_size, void* stream);
 /* Speaker-embedding size E of the loaded acoustic model (0: single speaker). */
 int tts_acoustic_speaker_dim(tts_engine* eng, int* dim);
 
@@ -459,6 +492,19 @@ int tts_op_durations(const float* logd, const int32_t* lens, int B, int N, const
  *   read and written. */
 int tts_op_var_embed_add(int dtype, void* x, int rows, int D, const float* e, const float* we, const float* be,
                          const float* p, const float* wp, const float* bp, void* stream);
+/* variance_adapt: the controlled forward's variance adaptor, one launch, one block per utterance
+ *   (len = min(lens[b], N), N <= 16383, Np >= N else refused).  logd (may be NULL with override_d),
+ *   pitch and energy are fp32 [B][Np]; override_d int32 [B][N] or NULL; ctl / ctl_size as for
+ *   tts_acoustic_forward_ctl (NULL: all neutral); we / be / wp / bp fp32 [D] as in var_embed_add.
+ *     dur [B][N], mel_lens [B], tokmap [B][Tcap]   durations' outputs with speed = duration_scale[b]
+ *     pitch, energy   tokens t < len rewritten in place by tts_prosody's formula, a neutral
+ *                     quantity left bit for bit; tokens t >= len neither read nor written
+ *     x [B][Np][D]    rows t < len get var_embed_add's rounding chain with the rewritten energy and
+ *                     pitch; rows t >= len are not touched */
+int tts_op_variance_adapt(int dtype, void* x, const float* logd, float* pitch, float* energy, const int32_t* lens,
+                          int B, int N, int Np, int D, const int32_t* override_d, const tts_prosody* ctl,
+                          size_t ctl_size, const float* we, const float* be, const float* wp, const float* bp, int Tcap,
+                          int32_t* dur, int32_t* mel_lens, int32_t* tokmap, void* stream);
 /* regulate: out[b][f][:] = round(fp32(enc[b][tokmap[b][f]][:]) * scale) for f < frames; enc [B][N][D]
  *   of dtype_in (dtype, or fp32 with a 16-bit dtype; another pair is refused), tokmap [B][Tcap] with
  *   entries < N, out [B][Tout][D], frames <= Tcap and <= Tout (else refused).  A frame whose token
