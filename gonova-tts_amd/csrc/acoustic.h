@@ -3,19 +3,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <functional>
 #include <string>
 #include <vector>
 
+#include "runtime.h"
+
 namespace tts {
 
-struct Profiler;
 struct VarianceCtl;  // acoustic_kernels.h: per-utterance prosody controls (device arrays)
 
 struct AcousticModel {
   bool loaded = false;
-  typedef std::function<const std::vector<float>*(const std::string&)> GetData;
-  typedef std::function<std::vector<int64_t>(const std::string&)> GetShape;
   // dtype: decoder / postnet activations; enc_dtype: encoder, speaker projection and variance
   // predictors (DT_F32 with a 16-bit dtype = split-precision GEMMs, TTS_ENCODER_EXACT);
   // f32_split_enc: an fp32 model's encoder side on the same split-precision GEMMs and attention

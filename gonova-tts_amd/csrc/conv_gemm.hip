@@ -8,7 +8,7 @@
 //     residual add + MRF sum/3 fused into the epilogue
 //     (oracle: oracle/vocoder.py resblock / vocoder_forward);
 //   * ConvTranspose1d upsamplers as polyphase convs (taps = k/s, M = s*Cout,
-//     output row n*s + m/Cout - p), see engine.cpp pack_transposed();
+//     output row n*s + m/Cout - p), see vocoder.cpp pack_transposed();
 //   * the acoustic model's FFN convs (k=3), linears (k=1), attention GEMMs.
 //
 // Layout in HBM: activations [B][rows][C] with C contiguous (one mel frame /

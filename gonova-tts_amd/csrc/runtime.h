@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -36,6 +37,11 @@ struct TtsError : std::runtime_error {
       throw ::tts::TtsError(TTS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     }                                                                                         \
   } while (0)
+
+// How a model's finalize reads the engine's host weights by name: the data (null when the name
+// was not set) and the shape (empty then)
+typedef std::function<const std::vector<float>*(const std::string&)> GetData;
+typedef std::function<std::vector<int64_t>(const std::string&)> GetShape;
 
 inline size_t dtype_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 
